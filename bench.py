@@ -13,10 +13,19 @@ decode-size slabs, reduce-scatter + all-gather for prefill chunks, SURVEY.md §8
 group's collective instead) and runs ONE request across them (strong scaling: per-token latency); value = that
 request's tokens / time.  `--gpus N` without WORLD_SIZE launches the N ranks itself (a torch.distributed.run child).
 
-Extra fields: prefill_ms, decode_tok_s, decode HBM fraction; "roofline" for the dominant
-kernel (the decode gate/up GEMV, HIP events on the stream it runs on); "cpu_baseline" = the
-oracle (numpy port of the reference path, fp32, vision re-run per token as the reference does)
-on a bounded sample, rank 0, N=1 only.
+A plain run does only what the headline needs: set-up, --warmup requests, --steps timed requests, the
+--dump-outputs files when asked for, and the result line (metric, value, unit, ms_per_step = the milliseconds
+one timed request took, dtype, the workload description).
+
+--dump-outputs DIR writes what the last timed request computed as DIR/<name>.npy (float32): `tokens` [B][T]
+(the generated ids, what generate() returns), `last_logits` [B][V] (the final decode step's logits) and
+`image_features` (the projected SigLIP rows of the request); an array too large for its share of 64 MB is stored
+as a fixed, seeded sample of its elements.  The inputs are seeded, so two builds can be compared file by file.
+
+--full adds everything else, each from runs of its own after the timed steps: prefill_ms, decode_tok_s, decode
+HBM fraction; "roofline" for the dominant kernel (the decode gate/up GEMV, HIP events on the stream it runs on);
+with N > 1 ranks the tensor-parallel legs; "cpu_baseline" = the oracle (numpy port of the reference path, fp32,
+vision re-run per token as the reference does) on a bounded sample, rank 0, N=1 only.
 """
 from __future__ import annotations
 
@@ -154,6 +163,36 @@ def cpu_baseline(cfg, ids, px, budget_tokens=24):
             "kind": "port",
             "sample": f"{len(out)} generated tokens of the same request (1 prefill L={ids.shape[1]} + "
                       f"{len(out) - 1} decode steps re-running SigLIP like the reference), fp32 numpy, {dt:.1f} s"}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """Write each tensor of `arrays` as dirname/<name>.npy in float32, DUMP_MAX_BYTES in all at most: an array over
+    its equal share is stored as a sample of its flattened elements at fixed, seeded (sorted) indices."""
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_MAX_BYTES // 4 // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(97531).integers(0, t.numel(), cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(t.float().cpu().numpy(), dtype=np.float32))
+
+
+def request_outputs(eng, state, B, T, tp):
+    """What the last request left for its caller: the generated ids [B][T] (the token history generate() returns),
+    the logits [B][V] of the final decode step (single-rank engines keep them in the decode workspace) and the
+    request's projected image features."""
+    out = {"tokens": state["st"]["hist"][:T].t(), "image_features": state["feats"]}
+    lg = eng._ws.get("d_logits")
+    if T > 1 and tp == 1 and lg is not None:
+        pad = eng.w.vocab_local_pad
+        out["last_logits"] = lg[:B * pad].view(B, pad)[:, :eng.w.vocab]
+    else:
+        log(f"[bench] --dump-outputs: no last_logits ({'a tensor-parallel rank holds only its vocabulary slice' if tp > 1 else 'the request ran no decode step'})")
+    return out
 
 
 class Runner:
@@ -391,11 +430,18 @@ def main():
     ap.add_argument("--fp8", action="store_true",
                     help="Gemma linears as fp8 e4m3 (per-channel / per-row scales) for GEMMs over 16 rows, as BASELINE "
                     "configs[4]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need, each in runs of its own: "
+                    "prefill-only / decode-only timings, the roofline kernel, the CPU baseline (N = 1) and the "
+                    "tensor-parallel legs (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (generated ids, final-step logits, image features) "
+                    "as DIR/<name>.npy, float32, 64 MB in all at most")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--graph-prefill", action="store_true",
                     help="replay the prefill as one hipGraph (measured 0.96-0.97x of eager launches: off by default)")
     ap.add_argument("--no-tp-curve", action="store_true",
-                    help="with --gpus N > 1 and --parallel dp: skip the extra tensor-parallel legs (the headline request "
+                    help="with --full, --gpus N > 1 and --parallel dp: skip the extra tensor-parallel legs (the headline request "
                     "over all N GPUs, BASELINE configs[3] at TP=2 and configs[4] at TP=N), reported beside the "
                     "data-parallel value")
     ap.add_argument("--sample", action="store_true", help="top-p sampling (T=0.8, p=0.9, uniforms seed 4321) "
@@ -484,51 +530,75 @@ def main():
     tokens = B * T * args.steps * (world // tp)
     value = tokens / elapsed
 
-    # prefill-only and decode-only timings (same stream, events)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    ev[0].record()
-    for _ in range(3):
-        prefill_run()
-    ev[1].record()
-    state["st"]["kv_len"].fill_(L)
-    state["st"]["pos"].fill_(L + 1)
-    state["st"]["step"].zero_()
-    ev[2].record()
-    for _ in range(T - 1):
-        replay()
-    ev[3].record()
-    torch.cuda.synchronize()
-    prefill_ms = ev[0].elapsed_time(ev[1]) / 3
-    decode_ms_tok = ev[2].elapsed_time(ev[3]) / (T - 1)
-    step_bytes = eng.w.decode_weight_bytes_fp8() if args.fp8 and B > 16 else eng.w.decode_weight_bytes()
-    kv_bytes = B * (L + T // 2) * eng.w.t_layers * 2 * eng.w.kv_heads * eng.w.head_dim * 2
-    decode_hbm = (step_bytes + kv_bytes) / (decode_ms_tok / 1e3) / 1e9
-    pf_flops = prefill_flops(cfg, B, L)
-    # roofline time of the prefill: fp8 flops (Gemma linears under --fp8) at the dense fp8 peak, the rest at bf16
-    f8 = gemma_linear_flops(cfg, B, L) if args.fp8 and B * L > 16 else 0
-    pf_ideal_s = (pf_flops - f8) / (BF16_PEAK_TFS * 1e12) + f8 / (FP8_PEAK_TFS * 1e12)
-
-    kern_s, kern_bytes = time_dominant_kernel(eng)
-    achieved = kern_bytes / kern_s / 1e9
-    traffic, traffic_src = pmc_traffic()
-    kern_desc = f"gemv_kernel<GELU_MUL,2> (decode gate/up, 2x{eng.w.inter}x{eng.w.hidden} bf16)"
+    if args.dump_outputs and rank == 0:
+        # what the last timed request computed, before anything else runs on the engine
+        dump_outputs(args.dump_outputs, request_outputs(eng, state, B, T, tp))
 
     comm_used = eng.comm
-    tp_recs = None
-    if world > 1 and tp == 1 and not args.no_tp_curve:
-        # the data-parallel engine is freed first (the TP legs build their own)
-        del state, eng, run, request, prefill_run, replay, sd
-        torch.cuda.empty_cache()
-        comm_used = None
-        tp_recs = {name: tp_leg(spec, rank, world, dist) for name, spec in tp_specs(world).items()}
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        del state, eng, run, request, prefill_run, replay
-        torch.cuda.empty_cache()
-        try:
-            cpu = cpu_baseline(cfg, ids_cpu, px_cpu)
-        except Exception as e:  # report, do not fail the bench
-            cpu = {"value": None, "unit": "tokens/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {e}"}
+    extra = {}
+    if args.full:
+        # prefill-only and decode-only timings (same stream, events)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+        for _ in range(3):
+            prefill_run()
+        ev[1].record()
+        state["st"]["kv_len"].fill_(L)
+        state["st"]["pos"].fill_(L + 1)
+        state["st"]["step"].zero_()
+        ev[2].record()
+        for _ in range(T - 1):
+            replay()
+        ev[3].record()
+        torch.cuda.synchronize()
+        prefill_ms = ev[0].elapsed_time(ev[1]) / 3
+        decode_ms_tok = ev[2].elapsed_time(ev[3]) / (T - 1)
+        step_bytes = eng.w.decode_weight_bytes_fp8() if args.fp8 and B > 16 else eng.w.decode_weight_bytes()
+        kv_bytes = B * (L + T // 2) * eng.w.t_layers * 2 * eng.w.kv_heads * eng.w.head_dim * 2
+        decode_hbm = (step_bytes + kv_bytes) / (decode_ms_tok / 1e3) / 1e9
+        pf_flops = prefill_flops(cfg, B, L)
+        # roofline time of the prefill: fp8 flops (Gemma linears under --fp8) at the dense fp8 peak, the rest at bf16
+        f8 = gemma_linear_flops(cfg, B, L) if args.fp8 and B * L > 16 else 0
+        pf_ideal_s = (pf_flops - f8) / (BF16_PEAK_TFS * 1e12) + f8 / (FP8_PEAK_TFS * 1e12)
+
+        kern_s, kern_bytes = time_dominant_kernel(eng)
+        achieved = kern_bytes / kern_s / 1e9
+        traffic, traffic_src = pmc_traffic()
+        kern_desc = f"gemv_kernel<GELU_MUL,2> (decode gate/up, 2x{eng.w.inter}x{eng.w.hidden} bf16)"
+
+        tp_recs = None
+        if world > 1 and tp == 1 and not args.no_tp_curve:
+            # the data-parallel engine is freed first (the TP legs build their own)
+            del state, eng, run, request, prefill_run, replay, sd
+            torch.cuda.empty_cache()
+            comm_used = None
+            tp_recs = {name: tp_leg(spec, rank, world, dist) for name, spec in tp_specs(world).items()}
+        cpu = None
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            del state, eng, run, request, prefill_run, replay
+            torch.cuda.empty_cache()
+            try:
+                cpu = cpu_baseline(cfg, ids_cpu, px_cpu)
+            except Exception as e:  # report, do not fail the bench
+                cpu = {"value": None, "unit": "tokens/s", "cores": os.cpu_count(), "kind": "port",
+                       "sample": f"failed: {e}"}
+        extra = {
+            "prefill_ms": round(prefill_ms, 3),
+            "prefill_tflops": round(pf_flops / (prefill_ms / 1e3) / 1e12, 2),
+            "prefill_mfma_frac": round(pf_ideal_s / (prefill_ms / 1e3), 4),
+            "decode_ms_per_token": round(decode_ms_tok, 4),
+            "decode_tok_s": round(B / (decode_ms_tok / 1e3), 1),
+            "decode_hbm_gbs": round(decode_hbm, 1),
+            "decode_hbm_frac": round(decode_hbm / HBM_PEAK_GBS, 4),
+            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                         "traffic_source": traffic_src,
+                         "kernel": kern_desc,
+                         "kernel_avg_us": round(kern_s * 1e6, 2), "bytes_per_launch": kern_bytes},
+            "cpu_baseline": cpu,
+        }
+        if tp_recs is not None:
+            extra.update(tp_recs)
 
     baseline_ref = {("pt-224", 1): "BASELINE.json configs[1]", ("pt-448", 16): "BASELINE.json configs[2]"}.get(
         (args.config, B), "not a BASELINE.json config")
@@ -548,22 +618,9 @@ def main():
                                    f"{T} {'top-p' if args.sample else 'greedy'} tokens ({baseline_ref})",
                        "global_batch": B * (world // tp), "seq_len": L + T,
                        "parallelism": f"dp{world}" if tp == 1 else f"tp{tp}-{args.comm}", "decode": graph_mode, "prefill": prefill_mode},
-            "prefill_ms": round(prefill_ms, 3),
-            "prefill_tflops": round(pf_flops / (prefill_ms / 1e3) / 1e12, 2),
-            "prefill_mfma_frac": round(pf_ideal_s / (prefill_ms / 1e3), 4),
-            "decode_ms_per_token": round(decode_ms_tok, 4),
-            "decode_tok_s": round(B / (decode_ms_tok / 1e3), 1),
-            "decode_hbm_gbs": round(decode_hbm, 1),
-            "decode_hbm_frac": round(decode_hbm / HBM_PEAK_GBS, 4),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "kernel": kern_desc,
-                         "kernel_avg_us": round(kern_s * 1e6, 2), "bytes_per_launch": kern_bytes},
-            "cpu_baseline": cpu,
+            "full": bool(args.full),
         }
-        if tp_recs is not None:
-            rec.update(tp_recs)
+        rec.update(extra)
         print(json.dumps(rec), flush=True)
     if comm_used is not None and hasattr(comm_used, "check"):
         comm_used.check()                      # a timed-out exchange invalidates the run

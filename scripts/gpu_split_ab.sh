@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-split_ab}; mkdir -p $O; : > $O/ab.jsonl
 for v in "" "PG_SPLIT_DOWN=4" "PG_SPLIT_O=1" "PG_SPLIT_O=4" "PG_SPLIT_O=8" ""; do
   echo "== ${v:-default}"
-  env $v timeout -k 10 240 python -u bench.py --no-cpu-baseline > $O/run.log 2>&1 || { tail -20 $O/run.log; exit 1; }
+  env $v timeout -k 10 240 python -u bench.py --full --no-cpu-baseline > $O/run.log 2>&1 || { tail -20 $O/run.log; exit 1; }
   python - "$v" $O <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[2] + "/run.log") if l.startswith("{")][-1]

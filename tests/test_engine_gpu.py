@@ -417,17 +417,21 @@ def test_pt224_free_running_greedy_ids_equal_reference(golden):
 
 
 @pytest.mark.gpu
-def test_bench_prints_one_contract_json_line():
-    """bench.py (the driver's contract): one JSON line on stdout with the required keys, BASELINE.json's metric and
-    configs[1] workload, a roofline object with achieved / peak / frac consistent with each other, and a
-    cpu_baseline object from the oracle port on a bounded sample (here 2 steps after 1 warmup)."""
+def test_bench_prints_one_contract_json_line(tmp_path):
+    """bench.py --full (the driver's contract): one JSON line on stdout with the required keys, BASELINE.json's metric
+    and configs[1] workload, a roofline object with achieved / peak / frac consistent with each other, and a
+    cpu_baseline object from the oracle port on a bounded sample (here 2 steps after 1 warmup).  --dump-outputs
+    leaves the last timed request's arrays as float32 .npy files: 128 in-vocabulary ids, finite logits whose argmax
+    is the last id, the 256 projected image rows.  A plain run prints the same line without the --full fields and
+    dumps the same arrays bit for bit."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1"],
-                       capture_output=True, text=True, timeout=280, cwd=root)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full",
+                        "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=280, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -444,3 +448,31 @@ def test_bench_prints_one_contract_json_line():
     assert 0 < rf["frac"] <= 1 and abs(rf["achieved"] / rf["peak"] - rf["frac"]) < 1e-3
     cb = o["cpu_baseline"]
     assert cb["kind"] in ("port", "reference") and cb["value"] and cb["value"] > 0 and cb["cores"] >= 1
+    out = {f[:-4]: np.load(dump / f) for f in sorted(os.listdir(dump))}
+    assert sorted(out) == ["image_features", "last_logits", "tokens"], sorted(out)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert out["tokens"].shape == (1, 128) and out["last_logits"].shape == (1, 257216)
+    assert out["image_features"].shape == (256, 2048)
+    assert (out["tokens"] == np.round(out["tokens"])).all() and out["tokens"].min() >= 0
+    assert int(out["last_logits"][0].argmax()) == int(out["tokens"][0, -1])
+    # a plain run (no --full): the same line without anything that takes runs of its own, and the same request's
+    # arrays, bit for bit (seeded inputs; the request computes the same thing whatever the step count)
+    dump2 = tmp_path / "outputs_plain"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
+                        "--dump-outputs", str(dump2)], capture_output=True, text=True, timeout=120, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    p = json.loads(lines[0])
+    assert p["full"] is False and o["full"] is True
+    assert p["steps"] == 1 and p["warmup"] == 0 and p["ms_per_step"] > 0 and p["value"] > 0
+    assert abs(p["value"] - 128 / (p["ms_per_step"] / 1e3)) < 1e-2 * p["value"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "scaling", "data", "config"):
+        assert p[k] == o[k], k
+    extras = ("prefill_ms", "prefill_tflops", "prefill_mfma_frac", "decode_ms_per_token", "decode_tok_s",
+              "decode_hbm_gbs", "decode_hbm_frac", "roofline", "cpu_baseline")
+    assert all(k in o for k in extras) and not any(k in p for k in extras), sorted(p)
+    assert sorted(os.listdir(dump2)) == sorted(os.listdir(dump))
+    for name, a in out.items():
+        assert np.array_equal(a, np.load(dump2 / (name + ".npy"))), name

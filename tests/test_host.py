@@ -315,6 +315,33 @@ def test_bench_refuses_world_size_other_than_gpus():
     assert r.returncode != 0 and "--gpus must be >= 1" in r.stderr, r.stderr[-2000:]
 
 
+def test_bench_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 .npy files within DUMP_MAX_BYTES in all; an array within its equal share is written
+    whole in its own shape, a larger one (a strided view and integer ids included) as its flattened elements at
+    sorted indices that are the same from call to call."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 * 4 * 1000)              # 1000 elements per array
+    big = torch.arange(60 * 50, dtype=torch.float64).reshape(60, 50).t()    # 3000 elements, not contiguous
+    arrays = {"small": torch.arange(12, dtype=torch.int64).reshape(3, 4), "big": big,
+              "edge": torch.arange(1000, dtype=torch.bfloat16)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "edge.npy", "small.npy"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(got["small"], np.arange(12, dtype=np.float32).reshape(3, 4))
+    assert np.array_equal(got["edge"], arrays["edge"].float().numpy())      # exactly its share: whole
+    flat = big.reshape(-1).numpy()
+    assert got["big"].shape == (1000,)
+    # the values are the flat indices of the transposed source: a sorted sample of the view's elements, in order
+    rows, cols = np.divmod(got["big"].astype(np.int64), 50)
+    pos = cols * 60 + rows
+    assert (np.diff(pos) >= 0).all() and np.array_equal(flat[pos], got["big"]) and len(set(pos.tolist())) > 500
+    for n in arrays:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy"))), n
+
+
 _SNIPPET = """
 0000000000001000 <k>:
 \tv_mfma_f32_16x16x32_bf16 a[0:3], v[6:9], v[10:13], 0     // 000000001000: D3B58000 02028906

@@ -25,12 +25,12 @@ def _port():
 
 
 def _launch(worker, tmp_path, nproc=2, timeout=600, **env):
-    # ranks sharing ONE device: at most 2 hardware queues per rank (TP_HW_QUEUES), so the 8 ranks' queues -- and this
-    # pytest process's own, which holds a context from the earlier tests -- all stay mapped at once.  An oversubscribed
-    # queue set is time-sliced, and a rank whose queue is not mapped cannot reach an exchange its peers spin in (an
-    # occasional 20 s xGMI timeout at 8 ranks x 4 queues in round 5; DESIGN §6 has the analysis).  A real node has a
-    # device per rank, at most 4 queues each.
-    env = dict(os.environ, TP_OUT=str(tmp_path), GPU_MAX_HW_QUEUES=os.environ.get("TP_HW_QUEUES", "2"), **env)
+    # ranks sharing ONE device run with 4 hardware queues each (TP_HW_QUEUES), HIP's own default: the xGMI ranks replay
+    # captured hipGraphs, and the exchange forks a side stream, so a graph can hold parallel branches; with fewer than
+    # 4 queues the HIP runtime can crash replaying such a graph.  (Round 5 saw one 20 s xGMI timeout at 8 ranks x 4
+    # queues and the launcher then went down to 2; the condition did not recur at 4 queues)  A real node
+    # has a device per rank.
+    env = dict(os.environ, TP_OUT=str(tmp_path), GPU_MAX_HW_QUEUES=os.environ.get("TP_HW_QUEUES", "4"), **env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr=127.0.0.1", f"--master-port={_port()}", os.path.join(ROOT, "tests", worker)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
@@ -170,16 +170,16 @@ def test_tp8_pt896_fp8_batch8(tmp_path):
 
 @pytest.mark.slow
 def test_bench_gpus2_launches_two_ranks():
-    """`python bench.py --gpus 2` with no launcher around it (the driver's N > 1 command line) starts two ranks as a
+    """`python bench.py --gpus 2 --full` with no launcher around it (the driver's N > 1 command line) starts two ranks as a
     torch.distributed.run child and relays rank 0's line: n_gpus 2, the data-parallel value, and the tensor-parallel
     legs (the headline request at TP=2, configs[3] top-p at TP=2, configs[4] pt-896 x32 fp8 at TP=2), none failed.
     The two ranks share this one device over gloo (PG_BENCH_BACKEND=gloo); on the 8-GPU node the backend is RCCL."""
     if not torch.cuda.is_available():
         pytest.skip("needs the HIP device")
-    env = dict(os.environ, PG_BENCH_BACKEND="gloo", GPU_MAX_HW_QUEUES="2")
+    env = dict(os.environ, PG_BENCH_BACKEND="gloo", GPU_MAX_HW_QUEUES="4")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
-                       env=env, capture_output=True, text=True, timeout=1100)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
+                        "--full"], env=env, capture_output=True, text=True, timeout=1100)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -88,6 +88,9 @@ def tiny(rank, world, name):
     W = synth.generate_state_dict(ocfg_)
     for B in sorted(int(k[1:-len("_logits")]) for k in g if k.startswith("b") and k.endswith("_logits")):
         p = f"b{B}_"
+        # the ranks finish the host-side oracle work below at different times (8 ranks share the host's cores); they
+        # meet here first, so no rank spins in an exchange kernel towards its 20 s timeout while a peer still computes
+        dist.barrier()
         ids = torch.from_numpy(g[p + "input_ids"]).cuda()
         px = torch.from_numpy(g[p + "pixel_values"]).cuda()
         Bv, L = ids.shape
@@ -114,6 +117,7 @@ def tiny(rank, world, name):
     ids = torch.from_numpy(g["b1_input_ids"]).cuda()
     px = torch.from_numpy(g["b1_pixel_values"]).cuda()
     am = torch.ones_like(ids)
+    dist.barrier()                                  # (after the last batch's oracle run, as above)
     out["greedy"] = tp.generate(ids, px, am, len(g["greedy_ids"]))[0].tolist()
     out["greedy_ref"] = g["greedy_ids"].tolist()
     out["greedy_solo"] = solo.generate(ids, px, am, len(g["greedy_ids"]))[0].tolist()
@@ -155,6 +159,7 @@ def tiny(rank, world, name):
         pxb = rng.standard_normal((Bd, 3, size, size)).astype(np.float32)
         ids_b = np.repeat(g["b1_input_ids"], Bd, 0)
         amb = np.ones_like(ids_b)
+        dist.barrier()
         c, f, lg0, n = tp.prefill_request(torch.from_numpy(ids_b).cuda(), torch.from_numpy(pxb).cuda(),
                                           torch.from_numpy(amb).cuda(), 4)
         s_ = tp.decode_state(Bd, c, n, 4)
@@ -174,6 +179,7 @@ def tiny(rank, world, name):
             tok = [5 + (7 * b + 11 * t) % 250 for b in range(Bd)]         # ordinary text ids (no image / pad id)
             s_["ids"].copy_(torch.tensor(tok, device="cuda"))
             s_["step"].zero_()
+            dist.barrier()                          # 48 oracle forwards per rank since the last exchange: meet first
             lgd = tp.decode_step(s_, c, f, samp).clone().cpu().numpy()
             L1 = ids_b.shape[1] + t + 1
             for b in range(Bd):
