@@ -12,7 +12,14 @@ HIP kernels:
                              (partials)] -> final RMSNorm -> lm_head GEMM(+bias)
   decode step                the same per token with the GEMV kernels, split-KV attention, argmax / top-p;
                              every per-step scalar (kv length, positions, step) lives in device memory,
-                             so one step is captured once as a hipGraph and replayed.
+                             so one step is captured once as a hipGraph and replayed.  The layers run in one
+                             of three forms (_decode_route):
+                               fin      one rank, bf16 rows, B <= FUSE_MAX_B or FIN_MIN_B <= B <= 16: o_proj and
+                                        down_proj finalise their split-K partials in-kernel (_decode_layers_fin);
+                               fused    B <= FUSE_MAX_B otherwise (tensor parallel, USE_FIN off): RMSNorm and
+                                        attention merge as GEMV prologues, fp32 slabs (_decode_layers_fused);
+                               unfused  every other batch (3..4 and > 16 rows, fp8 rows, TP above FUSE_MAX_B): norm
+                                        and merge as their own kernels (_decode_layers_unfused).
 
 Output-invariant deviations from the reference: the vision
 tower runs once per request instead of on every call (modeling_paligemma.py:281);
@@ -32,6 +39,7 @@ from __future__ import annotations
 
 import math
 import os
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -88,11 +96,10 @@ class PaliGemmaEngine:
     DECODE_SPLIT_O_SMALL = 2  # ... at B <= FUSE_MAX_B: split 2 (256 workgroups, tile finalised by the second arriver).
                               # Unsplit won earlier this round (1.120-1.122 vs 1.123-1.127 ms/token); with the q|k|v
                               # weights Infinity-Cache resident split 2 wins 7 of 8 interleaved pairs, -3.7 us mean
-                              # (scripts/r02/gpu_s3r.sh)
     # 5..16 rows on the in-kernel-finalised path (F32_FIN): o_proj unsplit and down_proj split 4 (pt-448 x16: 1.391 vs
     # 1.405 ms/step at 2 / 8, profiles/r05_decode_splits_pt448x16.jsonl); PG_SPLIT_O / PG_SPLIT_DOWN override
     DECODE_SPLIT_O_FIN16, DECODE_SPLIT_DOWN_FIN16 = 1, 4
-    DECODE_SPLIT_DOWN = 8   # split-K of down_proj at decode (8 vs 4: -4..6 us per pt-224 step, scripts/r02/gpu_t.sh)
+    DECODE_SPLIT_DOWN = 8   # split-K of down_proj at decode (8 vs 4: -4..6 us per pt-224 step)
     DECODE_SPLIT_KEYS = 32  # keys per wave in split-KV decode attention (one MFMA block)
     # keys per split at B <= FUSE_MAX_B: every o_proj workgroup merges all active splits in its prologue, so
     # fewer, longer splits (one wave per 32 keys, merged in LDS by attn_decode_wg_kernel) cut that re-read
@@ -103,9 +110,6 @@ class PaliGemmaEngine:
     TAIL_SPLIT = os.environ.get("PG_TAIL_SPLIT", "1") != "0"   # ... the tail with its own deeper split-K
     HEAD_KSPLIT = os.environ.get("PG_HEAD_KSPLIT", "1") != "0"  # ... and the split-K chosen for the head
     ROW_BLOCKS_GU = os.environ.get("PG_ROW_BLOCKS_GU", "1") != "0"  # gate/up (bf16 gelu*up) as row blocks too
-    # ragged-N SigLIP GEMMs as head + tail launches: measured neutral at pt-448 x16 and pt-896 x32 (the small-tile
-    # tail costs what the saved round gave back; scripts/tune/run_s4_p.sh), so off
-    COL_BLOCKS = os.environ.get("PG_COL_BLOCKS", "0") == "1"
     # batch-1 prefill (256 <= rows <= 288): these Gemma linears run as ONE row tile per 128 columns (PG_TILE_M1),
     # with this split-K -- each weight tile streams once instead of once per 256-row tile.  Per call at 264 rows
     # (scripts/tune/skinny_bench.py, profiles/r02_skinny_gemm_*.txt): gate/up 60.8 -> 52.8 us, down 38.9 -> 33.5,
@@ -116,10 +120,6 @@ class PaliGemmaEngine:
     TILE_M1_SPLIT = {"gu": 1, "down": int(os.environ.get("PG_M1_DOWN", "16"))}
     FUSE_MAX_B = 2          # decode batches up to this size fuse RMSNorm / attention merge into the GEMVs
     DECODE_SPLIT_TARGET = 1024  # B > FUSE_MAX_B: aim for about this many decode-attention splits (waves)
-    # long KV x batch: splits of several 32-key rounds per wave sized to one round of workgroups (_split_keys).
-    # Measured level with the 128-key splits (pt-896 x32: 51.8 vs 51.1 us per layer, attention + merge, same box;
-    # profiles/r03_decode_attn_bench.txt), so off
-    DECODE_ONE_ROUND = os.environ.get("PG_DECODE_ONE_ROUND", "0") == "1"
     FIN_MIN_B = 5           # FIN_MIN_B <= B <= 16: in-kernel finalisation with the merge as its own kernel
     USE_FIN = True          # single rank: split-K slabs finalised in-kernel (see _decode_layers_fin)
     # tensor parallel: SigLIP data-parallel over the images when every rank gets at least one (else replicated)
@@ -129,12 +129,6 @@ class PaliGemmaEngine:
     # chained greedy decode (single rank): the argmax's final launch also writes the next step's input rows
     # (pg_argmax_embed), so a decode step starts at layer 0 with no embed launch (decode_state(sampler=...))
     CHAIN_EMBED = os.environ.get("PG_CHAIN_EMBED", "1") != "0"
-    # 17..32-row fp8 decode: the down GEMV quantises h itself from the row maxima the gate/up epilogue collects
-    # (ops.gemm8_hx) instead of the pg_quant_fp8 launch between them.  Same bytes either way; measured slower at
-    # pt-896 x32 (r4 timelines: down 10.0 -> 15.7 us with 16 slabs, 18.0 with 8; gate/up +1.2 us for the
-    # atomics; the quantiser it removes costs 7.3 us), so off
-    HQ_FUSED = os.environ.get("PG_HQ_FUSED", "0") != "0"
-
     # 17..32-row fp8 decode MLP on MX rows: the gate/up epilogue writes h as e4m3 with one E8M0 scale per 32
     # columns (PgFusedArgs.mx_out) and the down GEMV reads those block scales into its MFMAs (mx_in) -- no
     # quantiser launch and no cross-workgroup row maximum (the block max stays inside one workgroup)
@@ -144,7 +138,8 @@ class PaliGemmaEngine:
     # rstd to its outputs.  Replaces the norm + per-row quantiser pair
     MX_NORM = os.environ.get("PG_MX_NORM", "1") != "0"
     # fp8 prefill MLP on MX h too (ABI 12): the 128 x 128 fp8 gate/up tile writes h as e4m3 + one E8M0 scale per 32
-    # columns (each wave owns one block per row) and the 256 x 256 fp8 down GEMM stages the block scales beside h --
+    # columns (each wave owns one block per row) and the 128 x 128 fp8 down GEMM (every MX launch runs on that tile)
+    # stages the block scales beside h --
     # the row quantiser launch between them (and half of h's bytes) is gone
     MX_PREFILL = os.environ.get("PG_MX_PREFILL", "1") != "0"
     # prefill linears that end a residual branch (SigLIP o / fc2, Gemma o / down) with ONE split on one rank add into
@@ -155,10 +150,6 @@ class PaliGemmaEngine:
     # slower (85.4-85.6 vs 84.9-85.1 ms; profiles/r06_prefill_res_ab.jsonl), so off there
     PREFILL_RES_MIN_M = int(os.environ.get("PG_PREFILL_RES_MIN_M", "65536"))
 
-    AMAX_LD = 32                     # one 128-B line per row maximum (the gate/up atomics of 32 rows spread out)
-    # 128-k chunks of h per down workgroup (8 or 16): bf16 h costs twice fp8's bytes per workgroup, so the split
-    # doubles instead (pt-896: 16 slabs of 8 chunks, as many x bytes per workgroup as the 8-slab fp8 route)
-    HQ_CHUNKS = int(os.environ.get("PG_HQ_CHUNKS", "8"))
     # B > FUSE_MAX_B: split-KV attention and its merge in one launch (pg_attn_decode; 0 = split kernel + combine)
     DECODE_FUSED_ATTN = os.environ.get("PG_DECODE_FUSED", "1") != "0"
     FUSED_MIN_ROUNDS = int(os.environ.get("PG_FUSED_MIN_ROUNDS", "2"))   # ... used from this many rounds per split on
@@ -176,7 +167,6 @@ class PaliGemmaEngine:
     # fp8 linears of 17..32 rows (batched decode, the lm_head of a 17..32-row batch) on the weight-streaming fp8 GEMV
     # (fragment-packed e4m3 weights, csrc/gemm.hip gemv8_kernel) instead of the LDS-staged fp8 tile GEMM
     FP8_GEMV = os.environ.get("PG_FP8_GEMV", "1") != "0"
-    DECODE_ADD_B32 = os.environ.get("PG_DECODE_ADD_B32", "0") == "1"   # (see _decode_layers_unfused)
 
     def __init__(self, cfg: dict, weights: PackedWeights, device="cuda", comm=None):
         self.cfg = cfg
@@ -186,12 +176,15 @@ class PaliGemmaEngine:
         self.tp = getattr(weights, "tp_world", 1)
         if self.comm.world != self.tp:
             raise ValueError(f"weights packed for tp_world={self.tp}, communicator has world {self.comm.world}")
+        # tuning overrides (None: unset) of the decode o_proj / down_proj split-K at every batch size (_decode_splits)
         self.split_o = self.DECODE_SPLIT_O if self.tp == 1 else 1        # smaller all-reduce messages under TP
-        if os.environ.get("PG_SPLIT_O"):                                   # tuning overrides
-            self.split_o = int(os.environ["PG_SPLIT_O"])
         self.split_down = self.DECODE_SPLIT_DOWN if self.tp == 1 else max(1, self.DECODE_SPLIT_DOWN // self.tp)
-        if os.environ.get("PG_SPLIT_DOWN"):
-            self.split_down = int(os.environ["PG_SPLIT_DOWN"])
+        env_o, env_d = os.environ.get("PG_SPLIT_O"), os.environ.get("PG_SPLIT_DOWN")    # tuning overrides
+        if env_o:
+            self.split_o = int(env_o)
+        if env_d:
+            self.split_down = int(env_d)
+        self._split_fixed = (bool(env_o), bool(env_d))  # an override holds at every batch size (_decode_splits)
         self._validate_splits()
         self.device = torch.device(device)
         self.image_token_id = cfg.get("image_token_index", 256000)
@@ -215,8 +208,6 @@ class PaliGemmaEngine:
                   ("down_proj (PG_SPLIT_DOWN)", self.split_down, w.inter, 8)]
         if self.TILE_M1:    # (a model too narrow for this split just skips the row-tile path, _tile_m1)
             checks.append(("batch-1 prefill down_proj (PG_M1_DOWN)", self.TILE_M1_SPLIT["down"], 64 * 64, 64))
-        if self.HQ_CHUNKS not in (8, 16):
-            raise ValueError(f"PG_HQ_CHUNKS {self.HQ_CHUNKS}: the bf16-h down GEMV stages 8 or 16 chunks")
         for what, ks, K, hi in checks:          # (a split past K's 64-wide chunks just computes a zero slab)
             if not 1 <= ks <= hi:
                 raise ValueError(f"split-K {ks} for {what}: needs 1 <= split <= {hi} (K = {K})")
@@ -290,17 +281,17 @@ class PaliGemmaEngine:
             ops.attention(qkv, 3 * hv, attn, hv, qkv[:, hv:], N * 3 * hv, hd, 3 * hv, vt, N, hd * (M + 32), M + 32,
                           B=B, Lq=N, Lkv=N, Hq=nh, Hkv=nh, D=hd, scale=1.0 / (hd ** 0.5), **ks_v)
             if res_o:
-                self._gemm_cols(attn, L["o_w"], resid, epi=ops.EPI_F32_RES, bias=L["o_b"])
+                ops.gemm(attn, L["o_w"], resid, epi=ops.EPI_F32_RES, bias=L["o_b"])
             else:
-                self._gemm_cols(attn, L["o_w"], part, epi=ops.EPI_F32, bias=L["o_b"], ksplit=s_o)
+                ops.gemm(attn, L["o_w"], part, epi=ops.EPI_F32, bias=L["o_b"], ksplit=s_o)
             ops.norm_residual(resid, L["ln2_w"], b=L["ln2_b"], mode=ops.NORM_LAYER, eps=w.v_eps, partials=part,
                               nsplit=0 if res_o else s_o, out=xn, write_resid=not res_o)
-            self._gemm_cols(xn, L["fc1_w"], h, epi=ops.EPI_BF16_GELU, bias=L["fc1_b"], split_m=Bs * N)
+            ops.gemm(xn, L["fc1_w"], h, epi=ops.EPI_BF16_GELU, bias=L["fc1_b"], split_m=Bs * N)
             if res_2:
-                self._gemm_cols(h, L["fc2_w"], resid, epi=ops.EPI_F32_RES, bias=L["fc2_b"])
+                ops.gemm(h, L["fc2_w"], resid, epi=ops.EPI_F32_RES, bias=L["fc2_b"])
                 ns = 0
             else:
-                self._gemm_cols(h, L["fc2_w"], part, epi=ops.EPI_F32, bias=L["fc2_b"], ksplit=s_2)
+                ops.gemm(h, L["fc2_w"], part, epi=ops.EPI_F32, bias=L["fc2_b"], ksplit=s_2)
                 ns = s_2
             if taps is not None:                                          # debug: residual after the layer
                 taps.append((resid + part[:ns].sum(0)).clone())
@@ -314,16 +305,20 @@ class PaliGemmaEngine:
         return (feats, hid) if want_hidden else feats
 
     # ------------------------------------------------------------------ Gemma stack (prefill, T = B*L rows)
+    def _embed_kw(self) -> dict:
+        """The constants every embedding launch takes (pg_embed_merge, pg_argmax_embed): the image and pad ids, the
+        image features' 1/sqrt(P) and the text rows' sqrt(H)."""
+        return dict(image_id=self.image_token_id, pad_id=self.pad_id, img_scale=float(self.w.proj_dim ** -0.5),
+                    normalizer=float(self.w.hidden ** 0.5))
+
     def embed_merge(self, input_ids: torch.Tensor, feats: torch.Tensor, out: torch.Tensor, rank=None):
-        w = self.w
         ids = input_ids.reshape(-1)
         n = ids.numel()
         if rank is None and n > 64:
             rank = self._buf("rank", (n,), torch.int32)
             ops.image_rank(ids, self.image_token_id, rank)
-        ops.embed_merge(ids, rank, w.embed, feats, feats.shape[0] if feats is not None else 0, out,
-                        image_id=self.image_token_id, pad_id=self.pad_id,
-                        img_scale=float(w.proj_dim ** -0.5), normalizer=float(w.hidden ** 0.5))
+        ops.embed_merge(ids, rank, self.w.embed, feats, feats.shape[0] if feats is not None else 0, out,
+                        **self._embed_kw())
 
     def gemma_prefill(self, x_resid: torch.Tensor, positions: torch.Tensor, cache: KVStore, B: int, L: int,
                       logits_rows: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
@@ -407,10 +402,8 @@ class PaliGemmaEngine:
         """(MX h, MX norms) for a B-row decode step: the 17..32-row fp8 GEMV path with the packed fp8 weights"""
         w = self.w
         L0 = w.tl[0]
-        base = (self.FP8_GEMV and self._fp8_rows(B) and B <= 32 and not self.HQ_FUSED and
-                not (self.tp == 1 and self.DECODE_ADD_B32))
-        mx_h = (base and self.MX_H and "gu_w8f" in L0 and "down_w8f" in L0 and w.inter % 128 == 0
-                and w.hidden <= 4096)
+        mx_h = (self.FP8_GEMV and self._fp8_rows(B) and B <= 32 and self.MX_H and "gu_w8f" in L0
+                and "down_w8f" in L0 and w.inter % 128 == 0 and w.hidden <= 4096)
         mx_n = (mx_h and self.MX_NORM and "qkv_w8f" in L0 and w.hidden % 1024 == 0
                 and getattr(w, "lm_w8f", None) is not None)
         return mx_h, mx_n
@@ -445,14 +438,11 @@ class PaliGemmaEngine:
              fa=None):
         """One Gemma linear: bf16 (fragment-packed W) or, with fp8 weights and M > 16, the activation rows
         quantised to e4m3 (pg_quant_fp8) feeding the PG_FP8 GEMM with the per-channel weight scales."""
-        w = self.w
         if isinstance(x, tuple) and x[0] == "mx":  # MX rows (e4m3 + [M][K/32] block scales): the tile GEMM
             return ops.gemm8(x[1], None, Lw[name + "_w8"], Lw[name + "_s8"], out, epi=epi, M=M, ksplit=ksplit, fa=fa,
                              mx_in=x[2])
         if not isinstance(x, tuple) and self._fp8_rows(M):
-            K = x.shape[1]
-            x8 = self._buf(f"x8_{K}", (M, K), torch.uint8)
-            xs = self._buf(f"xs_{K}", (M,), torch.float32)
+            x8, xs = self._x8(M, x.shape[1])
             ops.quant_fp8(x, x8, xs, M=M)
             x = (x8, xs)
         if isinstance(x, tuple):        # fp8 rows (quantised here, by _norm, or by the attention kernel)
@@ -461,64 +451,48 @@ class PaliGemmaEngine:
                 return ops.gemm8(x8, xs, Lw[name + "_w8f"], Lw[name + "_s8"], out, epi=epi, M=M, ksplit=ksplit,
                                  fa=fa, frag=True)
             return ops.gemm8(x8, xs, Lw[name + "_w8"], Lw[name + "_s8"], out, epi=epi, M=M, ksplit=ksplit, fa=fa)
-        W, flag = Lw[name + "_w"], w.wflag
+        W, flag = Lw[name + "_w"], self.w.wflag
         if M >= self.PREFILL_ROWMAJOR_MIN_M and name + "_wr" in Lw:
             W, flag = Lw[name + "_wr"], 0
             if fa is None and self._tile_m1(M, name) == ksplit:
                 return ops.gemm(x, W, out, epi=epi | ops.TILE_M1, ksplit=ksplit)
-        if fa is None and epi == ops.EPI_F32 and self.ROW_BLOCKS:
+        if fa is not None:
+            return ops.gemm_fused(x, W, out, fa, epi=epi | flag, M=M)
+        if epi == ops.EPI_F32 and self.ROW_BLOCKS:
             Mh = self._row_head(M, W.shape[0], ksplit)
             if Mh:
-                # the 256-row tiles of the first Mh rows fill whole rounds of CUs; the ragged last rows
-                # (pt-448 x16: 128 of 16512) run as a small GEMM instead of one more mostly idle round.
-                # Both write the same [ksplit][M][N] slabs (PgFusedArgs.slab_rows)
-                fr = ops.fused_args(slab_rows=M)
-                ops.gemm_fused(x[:Mh], W, out, fr, epi=epi | flag, M=Mh, ksplit=ksplit, ldc=out.stride(-2))
-                N, K, Mt = W.shape[0], W.shape[1], M - Mh
-                st = max(ksplit, ops.split_for(math.ceil(Mt / 64) * math.ceil(N / 128), K // 64, max_split=8))
-                if st > ksplit and self.TAIL_SPLIT:
-                    # the tail's own deeper split (its 64x128 tiles alone leave most CUs idle), summed into
-                    # slab 0's tail rows; the other slabs' tail rows are zeroed (the head never writes them)
-                    tp = self._buf("row_tail", (st, Mt, N), torch.float32)
-                    ops.gemm(x[Mh:M], W, tp, epi=epi | flag, ksplit=st)
-                    ops.slab_sum(tp, out[0, Mh:M])
-                    if ksplit > 1:
-                        out[1:ksplit, Mh:M].zero_()
-                    return out
-                tail = out.view(-1)[Mh * out.stride(-2):]
-                return ops.gemm_fused(x[Mh:M], W, tail, fr, epi=epi | flag, M=Mt, ksplit=ksplit,
-                                      ldc=out.stride(-2))
-        if fa is None and epi == ops.EPI_BF16_GELU_MUL and self.ROW_BLOCKS and self.ROW_BLOCKS_GU:
+                return self._lin_row_blocks(x, W, out, epi | flag, M, Mh, ksplit)
+        if epi == ops.EPI_BF16_GELU_MUL and self.ROW_BLOCKS and self.ROW_BLOCKS_GU:
             Mh = self._row_head(M, W.shape[0], 1)
             if Mh:      # gate/up at pt-448 x16: 8192 whole tiles (32 rounds) + a 128-row tail, not 33 rounds
                 ops.gemm(x[:Mh], W, out[:Mh], epi=epi | flag)
                 return ops.gemm(x[Mh:M], W, out[Mh:M], epi=epi | flag)
-        if fa is not None:
-            return ops.gemm_fused(x, W, out, fa, epi=epi | flag, M=M)
         return ops.gemm(x, W, out, epi=epi | flag, ksplit=ksplit)
 
-    def _gemm_cols(self, A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, *, epi: int, bias=None, ksplit: int = 1,
-                   split_m: Optional[int] = None):
-        """ops.gemm; or, when the last 256-column tile is ragged and dropping it saves a round of CUs, the whole
-        256-column tiles and the remaining columns as two GEMMs into the same output (column views: same ldc
-        and slab stride).  SigLIP o / fc1 / fc2 at pt-448 x16: 320 -> 256, 1088 -> 1024, 640 -> 512 tiles."""
-        Nh = self._col_head(A.shape[0], W.shape[0], ksplit) if self.COL_BLOCKS else 0
-        if not Nh:
-            return ops.gemm(A, W, out, epi=epi, bias=bias, ksplit=ksplit, split_m=split_m)
-        ops.gemm(A, W[:Nh], out[..., :Nh], epi=epi, bias=None if bias is None else bias[:Nh], ksplit=ksplit,
-                 split_m=split_m)
-        return ops.gemm(A, W[Nh:], out[..., Nh:], epi=epi, bias=None if bias is None else bias[Nh:], ksplit=ksplit,
-                        split_m=split_m)
+    def _lin_row_blocks(self, x: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epi: int, M: int, Mh: int,
+                        ksplit: int):
+        """A bf16 fp32-slab GEMM as a head of Mh rows (_row_head) and a tail: the 256-row tiles of the first Mh rows
+        fill whole rounds of CUs; the ragged last rows (pt-448 x16: 128 of 16512) run as a small GEMM instead of one
+        more mostly idle round.  Both write the same [ksplit][M][N] slabs (PgFusedArgs.slab_rows)."""
+        fr = ops.fused_args(slab_rows=M)
+        ops.gemm_fused(x[:Mh], W, out, fr, epi=epi, M=Mh, ksplit=ksplit, ldc=out.stride(-2))
+        N, K, Mt = W.shape[0], W.shape[1], M - Mh
+        st = max(ksplit, ops.split_for(math.ceil(Mt / 64) * math.ceil(N / 128), K // 64, max_split=8))
+        if st > ksplit and self.TAIL_SPLIT:
+            # the tail's own deeper split (its 64x128 tiles alone leave most CUs idle), summed into
+            # slab 0's tail rows; the other slabs' tail rows are zeroed (the head never writes them)
+            tp = self._buf("row_tail", (st, Mt, N), torch.float32)
+            ops.gemm(x[Mh:M], W, tp, epi=epi, ksplit=st)
+            ops.slab_sum(tp, out[0, Mh:M])
+            if ksplit > 1:
+                out[1:ksplit, Mh:M].zero_()
+            return out
+        tail = out.view(-1)[Mh * out.stride(-2):]
+        return ops.gemm_fused(x[Mh:M], W, tail, fr, epi=epi, M=Mt, ksplit=ksplit, ldc=out.stride(-2))
 
-    @staticmethod
-    def _col_head(M: int, N: int, ksplit: int, cus: int = ops.CUS) -> int:
-        """Columns to issue as whole 256-column tiles (0: one launch), in the one-tile-per-CU regime."""
-        Nh = N // 256 * 256
-        tm = (M + 255) // 256
-        if Nh == N or Nh == 0 or tm * ((N + 255) // 256) * ksplit < cus:
-            return 0
-        rounds = lambda tiles: (tiles + cus - 1) // cus  # noqa: E731
-        return Nh if rounds(tm * (Nh // 256) * ksplit) < rounds(tm * ((N + 255) // 256) * ksplit) else 0
+    def _x8(self, M: int, K: int) -> tuple:
+        """The (e4m3 rows [M][K], fp32 row scales [M]) buffers of an fp8 linear's K-wide input."""
+        return self._buf(f"x8_{K}", (M, K), torch.uint8), self._buf(f"xs_{K}", (M,), torch.float32)
 
     @staticmethod
     def _row_head(M: int, N: int, ksplit: int, cus: int = ops.CUS) -> int:
@@ -536,9 +510,7 @@ class PaliGemmaEngine:
         """Gemma RMSNorm of the residual (+ split-K partials) feeding a linear: bf16 rows, or fp8 rows with
         their scales (one launch, pg_norm_residual_fp8) when that linear runs on the fp8 path."""
         if self._fp8_rows(M):
-            H = resid.shape[-1]
-            x8 = self._buf(f"x8_{H}", (M, H), torch.uint8)
-            xs = self._buf(f"xs_{H}", (M,), torch.float32)
+            x8, xs = self._x8(M, resid.shape[-1])
             return ops.norm_residual_fp8(resid, norm_w, x8, xs, mode=ops.NORM_RMS, partials=part, nsplit=nsplit,
                                          write_resid=nsplit > 0)
         ops.norm_residual(resid, norm_w, mode=ops.NORM_RMS, partials=part, nsplit=nsplit, out=xn,
@@ -617,9 +589,7 @@ class PaliGemmaEngine:
             return ops.gemm8(x8, None, w.lm_w8f, w.lm_s8, out, epi=ops.EPI_F32, M=rows, bias=w.lm_bias, frag=True,
                              mx_in=xs, ss_in=ss)
         if self.FP8_GEMV and self._fp8_rows(rows) and rows <= 32 and getattr(w, "lm_w8f", None) is not None:
-            H = xf.shape[1]
-            x8 = self._buf(f"x8_{H}", (rows, H), torch.uint8)
-            xs = self._buf(f"xs_{H}", (rows,), torch.float32)
+            x8, xs = self._x8(rows, xf.shape[1])
             ops.quant_fp8(xf, x8, xs, M=rows)
             return ops.gemm8(x8, xs, w.lm_w8f, w.lm_s8, out, epi=ops.EPI_F32, M=rows, bias=w.lm_bias, frag=True)
         return ops.gemm(xf, w.lm_w, out, epi=ops.EPI_F32 | w.wflag, bias=w.lm_bias)
@@ -646,113 +616,144 @@ class PaliGemmaEngine:
         }
         return st
 
-    def decode_step(self, st: dict, cache: KVStore, feats: Optional[torch.Tensor], sampler: dict):
-        """One token for B rows: embed(ids) -> 18 layers -> lm_head -> argmax/top-p (advances the state).
+    def _decode_route(self, B: int) -> str:
+        """The form the layers of a B-row decode step take: "fin" (_decode_layers_fin), "fused"
+        (_decode_layers_fused) or "unfused" (_decode_layers_unfused)."""
+        fin_rows = B <= self.FUSE_MAX_B or self.FIN_MIN_B <= B <= 16
+        if self.tp == 1 and self.USE_FIN and fin_rows and not self._fp8_rows(B):
+            return "fin"
+        return "unfused" if B > self.FUSE_MAX_B else "fused"
 
-        Per layer 5 launches: [RMSNorm + q|k|v GEMV + RoPE + KV append] -> split-KV attention ->
-        [attention merge + o GEMV (split-K partials)] -> [RMSNorm + gate/up GEMV + gelu*mul] ->
-        down GEMV (split-K partials).  The residual stream ping-pongs between two fp32 buffers; the
-        RMSNorm prologues add the previous GEMV's split-K partials (deterministic order)."""
+    def _decode_splits(self, B: int, route: str) -> tuple:
+        """(o_proj, down_proj) split-K of a B-row decode step on `route`.  A PG_SPLIT_O / PG_SPLIT_DOWN override holds
+        everywhere; else 5..16 rows finalised in-kernel take the *_FIN16 pair, B <= FUSE_MAX_B on one rank takes
+        DECODE_SPLIT_O_SMALL, and everything else split_o / split_down."""
+        so, sd = self.split_o, self.split_down
+        fixed_o, fixed_d = self._split_fixed
+        if route == "fin" and B > self.FUSE_MAX_B:
+            so = so if fixed_o else self.DECODE_SPLIT_O_FIN16
+            sd = sd if fixed_d else self.DECODE_SPLIT_DOWN_FIN16
+        elif self.tp == 1 and B <= self.FUSE_MAX_B and not fixed_o:
+            so = self.DECODE_SPLIT_O_SMALL
+        return so, sd
+
+    def _decode_ws(self, B: int, cache: KVStore) -> SimpleNamespace:
+        """What a B-row decode step over `cache` fixes before its first launch: the layer form and its split-K pair,
+        the split-KV geometry (SK keys per split, nsplit splits, dt = head_dim padded to 16), the RoPE tables and the
+        buffers -- the residual pair res_a / res_b, normalised rows xn, q rows qb, MLP rows h, the o / down split-K
+        slabs part (as many as the route's deeper split writes) and the attention partials part_o / part_ml."""
         w = self.w
-        B = st["ids"].numel()
-        H, I, nh, nkv, hd = w.hidden, w.inter, w.heads, w.kv_heads, w.head_dim
-        kvd = nkv * hd
+        H, nh, nkv, hd = w.hidden, w.heads, w.kv_heads, w.head_dim
+        route = self._decode_route(B)
+        so, sd = self._decode_splits(B, route)
         cos_t, sin_t = self.rope(cache.Smax + 2)
-        res_a = self._buf("d_res_a", (B, H), torch.float32)
-        res_b = self._buf("d_res_b", (B, H), torch.float32)
-        xn = self._buf("d_xn", (B, H), torch.bfloat16)
-        qb = self._buf("d_q", (B, nh * hd), torch.bfloat16)
-        h = self._buf("d_h", (B, I), torch.bfloat16)
-        so, sd = self._split_o(B), self.split_down
-        part = self._buf("d_part", (max(so, sd, 16), B, H), torch.float32)     # (16: the gemm8_hx down path)
         SK = self._split_keys(B, cache.Smax)
         nsplit = _rup((cache.Smax + SK - 1) // SK, 4)
         dt = (hd + 15) // 16 * 16
         ns_ws = max(nsplit, ops.decode_plan(B, nkv, cache.Smax)[0]) if B > self.FUSE_MAX_B else nsplit
-        part_o = self._buf("d_po", (B * nkv * ns_ws * 16 * dt,), torch.float32)
-        part_ml = self._buf("d_pml", (B * nkv * ns_ws * 16 * 2,), torch.float32)
+        return SimpleNamespace(
+            B=B, route=route, so=so, sd=sd, SK=SK, nsplit=nsplit, dt=dt, cos_t=cos_t, sin_t=sin_t,
+            res_a=self._buf("d_res_a", (B, H), torch.float32),
+            res_b=self._buf("d_res_b", (B, H), torch.float32),
+            xn=self._buf("d_xn", (B, H), torch.bfloat16),
+            qb=self._buf("d_q", (B, nh * hd), torch.bfloat16),
+            h=self._buf("d_h", (B, w.inter), torch.bfloat16),
+            part=self._buf("d_part", (max(so, sd), B, H), torch.float32),
+            part_o=self._buf("d_po", (B * nkv * ns_ws * 16 * dt,), torch.float32),
+            part_ml=self._buf("d_pml", (B * nkv * ns_ws * 16 * 2,), torch.float32))
+
+    def decode_step(self, st: dict, cache: KVStore, feats: Optional[torch.Tensor], sampler: dict):
+        """One token for B rows: embed(ids) -> 18 layers -> lm_head -> argmax/top-p (advances the state).  The layers
+        run in the form _decode_route picks for B, on the buffers and splits of one _decode_ws record."""
+        w = self.w
+        B = st["ids"].numel()
+        ws = self._decode_ws(B, cache)
         chain = bool(st.get("chain")) and self._chain_ok(sampler)
         if not chain:                               # chained: the previous sample() wrote res_a already
-            ops.embed_merge(st["ids"], None, w.embed, feats, feats.shape[0] if feats is not None else 0, res_a,
-                            image_id=self.image_token_id, pad_id=self.pad_id, img_scale=float(w.proj_dim ** -0.5),
-                            normalizer=float(w.hidden ** 0.5))
-        ns = 0
-        fin = self.tp == 1 and self.USE_FIN and (B <= self.FUSE_MAX_B or self.FIN_MIN_B <= B <= 16) and \
-            not self._fp8_rows(B)
-        if B > self.FUSE_MAX_B and not fin:
-            ns = self._decode_layers_unfused(st, cache, res_a, xn, qb, h, part, part_o, part_ml, nsplit, dt, cos_t,
-                                             sin_t, SK)
-        if fin:
-            xq, ss, tiles, n_ss = self._decode_layers_fin(st, cache, res_a, qb, h, part, part_o, part_ml, nsplit, dt,
-                                                          cos_t, sin_t, SK)
+            ops.embed_merge(st["ids"], None, w.embed, feats, feats.shape[0] if feats is not None else 0, ws.res_a,
+                            **self._embed_kw())
+        if ws.route == "fin":
+            xq, ss, tiles, n_ss = self._decode_layers_fin(st, cache, ws)
             # final RMSNorm folded into the lm_head GEMV: x' = resid*(1+w) from the last down_proj, rstd on the outputs
             logits = self._buf("d_logits", (B, w.vocab_local_pad), torch.float32)
             fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=ss, ss_ld=tiles, ss_n=n_ss, eps=1e-6)
             ops.gemm_fused(xq, w.lm_w, logits, fa, epi=ops.EPI_F32 | w.wflag, M=B, bias=w.lm_bias)
             logits = logits[:, :w.vocab]
-            if sampler is not None:
-                self.sample(logits, st, sampler, advance=True, feats=feats)
-            return logits
-        for i, Lw in enumerate(w.tl if B <= self.FUSE_MAX_B else ()):      # (TP / USE_FIN off, B <= FUSE_MAX_B)
-            fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res_a, resid_out=res_b, partials=part, nsplit=ns,
-                                norm_w=Lw["in_w"], eps=1e-6, head_dim=hd, cos_t=cos_t, sin_t=sin_t, pos=st["pos"],
-                                rows_per_batch=1, slot_dev=st["kv_len"], slot_base=0, kc=cache.k[i],
-                                vtc=cache.vt[i], smax=cache.Smax, q_heads=nh, kv_heads=nkv, kd=cache.kd[i],
-                                vd=cache.vd[i])
-            ops.gemm_fused(None, Lw["qkv_w"], qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag, M=B)
-            ops.attention(qb, nh * hd, None, nh * hd, cache.k[i], cache.Smax * kvd, hd, kvd,
-                          cache.vt[i], kvd * cache.Smax, hd * cache.Smax, cache.Smax,
-                          B=B, Lq=1, Lkv=1, lkv_dev=st["kv_len"], Hq=nh, Hkv=nkv, D=hd,
-                          scale=1.0 / math.sqrt(hd), split_keys=SK, nsplit=nsplit, part_o=part_o, part_ml=part_ml,
-                          kcap=cache.Smax, kd=cache.kd[i], vd=cache.vd[i])
-            fa = ops.fused_args(pro_mode=ops.PRO_ATTN_COMBINE, part_o=part_o, part_ml=part_ml, asplit=nsplit,
-                                head_dim=hd, dtw=dt, q_per_kv=nh // nkv, kv_heads=nkv, slot_dev=st["kv_len"],
-                                akeys=SK)
-            ops.gemm_fused(None, Lw["o_w"], part, fa, epi=ops.EPI_F32 | w.wflag, M=B, ksplit=so)
-            n_o = self._allreduce_slabs(part, so)
-            fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res_b, resid_out=res_a, partials=part, nsplit=n_o,
-                                norm_w=Lw["post_w"], eps=1e-6)
-            ops.gemm_fused(None, Lw["gu_w"], h, fa, epi=ops.EPI_BF16_GELU_MUL | w.wflag, M=B)
-            ops.gemm(h, Lw["down_w"], part, epi=ops.EPI_F32 | w.wflag, ksplit=sd)
-            ns = self._allreduce_slabs(part, sd)
-        if B > self.FUSE_MAX_B and self._mx_decode(B)[1]:   # MX rows for the fp8 lm_head (it applies rstd)
-            H = w.hidden
-            xn = ("mx",) + ops.norm_residual_mx(res_a, w.final_w, self._buf("d_x8n", (B, H), torch.uint8),
-                                                self._buf("d_xsn", (B * H // 32,), torch.uint8),
-                                                self._buf("d_ssn", (B, H // 1024), torch.float32), partials=part,
-                                                nsplit=ns, write_resid=False)
         else:
-            ops.norm_residual(res_a, w.final_w, mode=ops.NORM_RMS, partials=part, nsplit=ns, out=xn,
-                              write_resid=False)
-        if self.tp > 1 and sampler is not None and not sampler.get("do_sample"):
-            # vocabulary-parallel greedy: local (max, index) pairs -> all-reduce of the zeroed slots -> merge
-            loc = self._buf("d_logits_loc", (B, w.vocab_local_pad), torch.float32)
-            self._lm_gemm(xn, B, loc)
-            loc = loc[:, :w.vocab_local]
-            Bp = B + (B & 1)                    # whole 16-byte exchange units (pairs of rows)
-            mine = self._buf("d_pairs_loc", (Bp, 2), torch.float32)
-            ops.argmax_pairs(loc, st["ws"], mine, vocab_offset=w.vocab_offset)
-            pairs = self._buf("d_pairs", (self.tp, Bp, 2), torch.float32)
-            self.comm.all_gather(pairs, mine)
-            if Bp != B:
-                pairs = self._buf("d_pairs_b", (self.tp, B, 2), torch.float32).copy_(pairs[:, :B])
-            ops.argmax_merge(pairs, st["ids"], world=self.tp, hist=st["hist"], step=st["step"], pos=st["pos"],
-                             kv_len=st["kv_len"])
-            return loc
-        logits = self.lm_head(xn, B, name="d_logits")
+            layers = self._decode_layers_fused if ws.route == "fused" else self._decode_layers_unfused
+            ns = layers(st, cache, ws)
+            xn = ws.xn
+            if ws.route == "unfused" and self._mx_decode(B)[1]:   # MX rows for the fp8 lm_head (it applies rstd)
+                H = w.hidden
+                xn = ("mx",) + ops.norm_residual_mx(ws.res_a, w.final_w, self._buf("d_x8n", (B, H), torch.uint8),
+                                                    self._buf("d_xsn", (B * H // 32,), torch.uint8),
+                                                    self._buf("d_ssn", (B, H // 1024), torch.float32),
+                                                    partials=ws.part, nsplit=ns, write_resid=False)
+            else:
+                ops.norm_residual(ws.res_a, w.final_w, mode=ops.NORM_RMS, partials=ws.part, nsplit=ns, out=xn,
+                                  write_resid=False)
+            if self.tp > 1 and sampler is not None and not sampler.get("do_sample"):
+                return self._tp_greedy(xn, st)
+            logits = self.lm_head(xn, B, name="d_logits")
         if sampler is not None:
             self.sample(logits, st, sampler, advance=True, feats=feats)
         return logits
 
-    def _decode_attn_merged(self, i, st, cache, qb, attn, part_o, part_ml, SK, nsplit, want_fp8=False):
-        """Split-KV decode attention of layer i for B > FUSE_MAX_B rows, merged into attn bf16 [B][nh*hd]: one
-        pg_attn_decode launch (DECODE_FUSED_ATTN), else the split kernel + pg_attn_combine.  want_fp8: return the
-        rows also as (e4m3, row scales) when the one-launch kernel can write them (the fp8 o_proj's input, no
-        quantiser launch), else None."""
+    def _tp_greedy(self, xn, st: dict) -> torch.Tensor:
+        """Vocabulary-parallel greedy sampling from the normalised rows: local (max, index) pairs -> all-gather ->
+        merge (advances the state).  Returns this rank's logits slice [B][vocab_local]."""
         w = self.w
-        B = qb.shape[0]
+        B = st["ids"].numel()
+        loc = self._buf("d_logits_loc", (B, w.vocab_local_pad), torch.float32)
+        self._lm_gemm(xn, B, loc)
+        loc = loc[:, :w.vocab_local]
+        Bp = B + (B & 1)                    # whole 16-byte exchange units (pairs of rows)
+        mine = self._buf("d_pairs_loc", (Bp, 2), torch.float32)
+        ops.argmax_pairs(loc, st["ws"], mine, vocab_offset=w.vocab_offset)
+        pairs = self._buf("d_pairs", (self.tp, Bp, 2), torch.float32)
+        self.comm.all_gather(pairs, mine)
+        if Bp != B:
+            pairs = self._buf("d_pairs_b", (self.tp, B, 2), torch.float32).copy_(pairs[:, :B])
+        ops.argmax_merge(pairs, st["ids"], world=self.tp, hist=st["hist"], step=st["step"], pos=st["pos"],
+                         kv_len=st["kv_len"])
+        return loc
+
+    # ---- what the three layer forms share: layer i's RoPE / KV-append arguments, its split-KV attention, the merge
+    def _rope_kw(self, i: int, st: dict, cache: KVStore, ws) -> dict:
+        """PgFusedArgs fields of layer i's decode q|k|v epilogue: RoPE at the rows' positions, K / V appended at the
+        device-resident kv length (canonical and decode-order copies)."""
+        w = self.w
+        return dict(head_dim=w.head_dim, cos_t=ws.cos_t, sin_t=ws.sin_t, pos=st["pos"], rows_per_batch=1,
+                    slot_dev=st["kv_len"], slot_base=0, kc=cache.k[i], vtc=cache.vt[i], smax=cache.Smax,
+                    q_heads=w.heads, kv_heads=w.kv_heads, kd=cache.kd[i], vd=cache.vd[i])
+
+    def _attn_split(self, i: int, st: dict, cache: KVStore, ws):
+        """Layer i's split-KV decode attention: the (O, m, l) partials of ws.nsplit splits of ws.SK keys."""
+        w = self.w
         nh, nkv, hd = w.heads, w.kv_heads, w.head_dim
         kvd = nkv * hd
+        ops.attention(ws.qb, nh * hd, None, nh * hd, cache.k[i], cache.Smax * kvd, hd, kvd,
+                      cache.vt[i], kvd * cache.Smax, hd * cache.Smax, cache.Smax,
+                      B=ws.B, Lq=1, Lkv=1, lkv_dev=st["kv_len"], Hq=nh, Hkv=nkv, D=hd,
+                      scale=1.0 / math.sqrt(hd), split_keys=ws.SK, nsplit=ws.nsplit, part_o=ws.part_o,
+                      part_ml=ws.part_ml, kcap=cache.Smax, kd=cache.kd[i], vd=cache.vd[i])
+
+    def _combine_kw(self, st: dict, ws) -> dict:
+        """PgFusedArgs fields of an o_proj GEMV that merges the split-KV partials in its prologue."""
+        w = self.w
+        return dict(pro_mode=ops.PRO_ATTN_COMBINE, part_o=ws.part_o, part_ml=ws.part_ml, asplit=ws.nsplit,
+                    head_dim=w.head_dim, dtw=ws.dt, q_per_kv=w.heads // w.kv_heads, kv_heads=w.kv_heads,
+                    slot_dev=st["kv_len"], akeys=ws.SK)
+
+    def _decode_attn_merged(self, i: int, st: dict, cache: KVStore, ws, want_fp8: bool = False):
+        """Split-KV decode attention of layer i for B > FUSE_MAX_B rows, merged: one pg_attn_decode launch
+        (DECODE_FUSED_ATTN), else the split kernel + pg_attn_combine.  Returns the o_proj's input: the rows as bf16
+        [B][nh*hd], or with want_fp8, when the one-launch kernel can write them, as (e4m3, row scales) -- no
+        quantiser launch."""
+        w = self.w
+        B = ws.B
+        nh, nkv, hd = w.heads, w.kv_heads, w.head_dim
+        attn = self._buf("d_attn", (B, nh * hd), torch.bfloat16)
         # the one-launch kernel where the cache needs several rounds of waves (pt-896 x32: 34.3 vs 43.3 us per layer,
         # attention + merge); with one round its last split's serial merge of every partial costs more than the
         # combine launch (pt-224 x16 1.374 vs 1.350 ms/step, round 4).  Since round 5's cheaper merge tail (8 partials
@@ -762,26 +763,16 @@ class PaliGemmaEngine:
         if self.DECODE_FUSED_ATTN and hd in (32, 256) and cache.Smax >= 64 and plan[2] >= self.FUSED_MIN_ROUNDS:
             x8 = None
             if want_fp8 and self.ATTN_FP8_OUT and ops.attn_decode_q8_ok(nh, nkv, hd, plan[1]):
-                x8 = (self._buf(f"x8_{nh * hd}", (B, nh * hd), torch.uint8), self._buf(f"xs_{nh * hd}", (B,),
-                                                                                     torch.float32))
-            ops.attn_decode(qb, nh * hd, attn, nh * hd, cache.kd[i], cache.vd[i],
+                x8 = self._x8(B, nh * hd)
+            ops.attn_decode(ws.qb, nh * hd, attn, nh * hd, cache.kd[i], cache.vd[i],
                             B=B, Lkv=1, lkv_dev=st["kv_len"], Hq=nh, Hkv=nkv, D=hd, scale=1.0 / math.sqrt(hd),
-                            kcap=cache.Smax, part_o=part_o, part_ml=part_ml,
+                            kcap=cache.Smax, part_o=ws.part_o, part_ml=ws.part_ml,
                             counters=self._zeros("d_dec_cnt", (B * nkv,), torch.int32), plan=plan,
                             q8=x8[0] if x8 else None, q8_scale=x8[1] if x8 else None)
-            return x8
-        ops.attention(qb, nh * hd, None, nh * hd, cache.k[i], cache.Smax * kvd, hd, kvd,
-                      cache.vt[i], kvd * cache.Smax, hd * cache.Smax, cache.Smax,
-                      B=B, Lq=1, Lkv=1, lkv_dev=st["kv_len"], Hq=nh, Hkv=nkv, D=hd,
-                      scale=1.0 / math.sqrt(hd), split_keys=SK, nsplit=nsplit, part_o=part_o,
-                      part_ml=part_ml, kcap=cache.Smax, kd=cache.kd[i], vd=cache.vd[i])
-        ops.attn_combine(part_o, part_ml, attn, nh * hd, B=B, Hq=nh, Hkv=nkv, D=hd, nsplit=nsplit)
-        return None
-
-    def _split_o(self, B: int) -> int:
-        if self.tp == 1 and B <= self.FUSE_MAX_B and not os.environ.get("PG_SPLIT_O"):
-            return self.DECODE_SPLIT_O_SMALL
-        return self.split_o
+            return x8 or attn
+        self._attn_split(i, st, cache, ws)
+        ops.attn_combine(ws.part_o, ws.part_ml, attn, nh * hd, B=B, Hq=nh, Hkv=nkv, D=hd, nsplit=ws.nsplit)
+        return attn
 
     def fx_status(self) -> torch.Tensor:
         """The fixed-point residual's status word (PgFusedArgs.status): an FX_ADD launch sets it when a value is
@@ -804,7 +795,31 @@ class PaliGemmaEngine:
             self._ws[name] = t
         return t
 
-    def _decode_layers_fin(self, st, cache, res, qb, h, part, part_o, part_ml, nsplit, dt, cos_t, sin_t, SK=None):
+    def _decode_layers_fused(self, st: dict, cache: KVStore, ws) -> int:
+        """Decode layers for B <= FUSE_MAX_B under tensor parallelism (or USE_FIN off), 5 launches each:
+        [RMSNorm + q|k|v GEMV + RoPE + KV append] -> split-KV attention -> [attention merge + o GEMV (split-K
+        partials)] -> [RMSNorm + gate/up GEMV + gelu*mul] -> down GEMV (split-K partials).  The residual stream
+        ping-pongs between two fp32 buffers; the RMSNorm prologues add the previous GEMV's split-K partials
+        (deterministic order).  Returns the slab count the final norm must add."""
+        w = self.w
+        B, res_a, res_b, part = ws.B, ws.res_a, ws.res_b, ws.part
+        ns = 0
+        for i, Lw in enumerate(w.tl):
+            fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res_a, resid_out=res_b, partials=part, nsplit=ns,
+                                norm_w=Lw["in_w"], eps=1e-6, **self._rope_kw(i, st, cache, ws))
+            ops.gemm_fused(None, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag, M=B)
+            self._attn_split(i, st, cache, ws)
+            fa = ops.fused_args(**self._combine_kw(st, ws))
+            ops.gemm_fused(None, Lw["o_w"], part, fa, epi=ops.EPI_F32 | w.wflag, M=B, ksplit=ws.so)
+            n_o = self._allreduce_slabs(part, ws.so)
+            fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res_b, resid_out=res_a, partials=part, nsplit=n_o,
+                                norm_w=Lw["post_w"], eps=1e-6)
+            ops.gemm_fused(None, Lw["gu_w"], ws.h, fa, epi=ops.EPI_BF16_GELU_MUL | w.wflag, M=B)
+            ops.gemm(ws.h, Lw["down_w"], part, epi=ops.EPI_F32 | w.wflag, ksplit=ws.sd)
+            ns = self._allreduce_slabs(part, ws.sd)
+        return ns
+
+    def _decode_layers_fin(self, st: dict, cache: KVStore, ws):
         """Decode layers (single rank, B <= FUSE_MAX_B) in 5 launches with in-kernel split-K finalisation:
         o_proj and down_proj add their split-K slabs into the residual in place (the last-arriving split of
         each 16-column tile), and write x' = bf16(resid*(1+w_next)) plus per-tile sums of squares; the next
@@ -815,37 +830,30 @@ class PaliGemmaEngine:
         the sums of squares come one per tile pair.
         Returns (x', sums of squares, their row stride, entries per row) of the final norm for the lm_head."""
         w = self.w
-        B = st["ids"].numel()
-        H, nh, nkv, hd = w.hidden, w.heads, w.kv_heads, w.head_dim
-        kvd = nkv * hd
-        so, sd = self._split_o(B), self.split_down
-        if B > self.FUSE_MAX_B and self.tp == 1:
-            if not os.environ.get("PG_SPLIT_O"):
-                so = self.DECODE_SPLIT_O_FIN16
-            if not os.environ.get("PG_SPLIT_DOWN"):
-                sd = self.DECODE_SPLIT_DOWN_FIN16
+        B, res, part = ws.B, ws.res_a, ws.part
+        H = w.hidden
         tiles = (H + 15) // 16
-        n_ss = tiles if B <= 4 else (tiles + 1) // 2         # one entry per GEMV workgroup (M > 4: tile pairs)
         merge_in_gemv = B <= self.FUSE_MAX_B
-        attn = None if merge_in_gemv else self._buf("d_attn", (B, nh * hd), torch.bfloat16)
-        cnt = self._zeros("d_fin_cnt", (tiles,), torch.int32)
-        ss_o = self._buf("d_ss_o", (B, tiles), torch.float32)
-        ss_d = self._buf("d_ss_d", (B, tiles), torch.float32)
-        xq = self._buf("d_xq", (B, H), torch.bfloat16)
-        SK = SK or self.DECODE_SPLIT_KEYS
-        nl = len(w.tl)
-        add_down = merge_in_gemv and self.DECODE_ADD in ("down", "both", "fx")
-        add_o = merge_in_gemv and self.DECODE_ADD in ("both", "fx")
         # "fx": the partials go to the fixed-point accumulator (zero between steps: the last layer's F32_FIN clears it);
         # layer 0's o_proj also folds the embedding rows in, so from there on it holds the whole residual
         fx = self._zeros("d_fx", (B, H), torch.int64) if merge_in_gemv and self.DECODE_ADD == "fx" else None
-        fx_st = self.fx_status() if fx is not None else None      # set by an FX_ADD launch given an unholdable value
-        add_epi, add_dst = (ops.EPI_FX_ADD, fx) if fx is not None else (ops.EPI_F32_ADD, res)
+        f = SimpleNamespace(                        # what _mlp_fin shares with this loop
+            tiles=tiles,
+            n_ss=tiles if B <= 4 else (tiles + 1) // 2,         # one entry per GEMV workgroup (M > 4: tile pairs)
+            cnt=self._zeros("d_fin_cnt", (tiles,), torch.int32),
+            ss_o=self._buf("d_ss_o", (B, tiles), torch.float32),
+            ss_d=self._buf("d_ss_d", (B, tiles), torch.float32),
+            xq=self._buf("d_xq", (B, H), torch.bfloat16),
+            add_down=merge_in_gemv and self.DECODE_ADD in ("down", "both", "fx"),
+            add_o=merge_in_gemv and self.DECODE_ADD in ("both", "fx"),
+            fx=fx,
+            fx_st=self.fx_status() if fx is not None else None,  # set by an FX_ADD launch given an unholdable value
+            add_epi=ops.EPI_FX_ADD if fx is not None else ops.EPI_F32_ADD,
+            add_dst=fx if fx is not None else res)
+        fin_o = dict(fin_cnt=f.cnt, fin_resid=res, ss_out=f.ss_o, ss_ld=tiles, fin_x=f.xq)  # o_proj's F32_FIN fields
         for i, Lw in enumerate(w.tl):
-            rope = dict(head_dim=hd, cos_t=cos_t, sin_t=sin_t, pos=st["pos"], rows_per_batch=1,
-                        slot_dev=st["kv_len"], slot_base=0, kc=cache.k[i], vtc=cache.vt[i], smax=cache.Smax,
-                        q_heads=nh, kv_heads=nkv, kd=cache.kd[i], vd=cache.vd[i])
-            if i == 0 or add_down:  # the residual rows are final (embedding, or atomically added): RMSNorm prologue
+            rope = self._rope_kw(i, st, cache, ws)
+            if i == 0 or f.add_down:  # the residual rows are final (embedding, or atomically added): RMSNorm prologue
                 # (fx mode: layer 0 reads the embedding rows; from layer 0's o_proj on the accumulator holds the whole
                 # residual -- that launch folds res in -- and the consumers read it alone)
                 fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res if (i == 0 or fx is None) else None,
@@ -854,61 +862,50 @@ class PaliGemmaEngine:
                     # the step starts from a zero accumulator whatever an earlier (interrupted) step left in it: layer 0's
                     # q|k|v GEMV does not read it and clears it before layer 0's o_proj adds into it
                     fa.amax_zero, fa.amax_zero_n = fx.data_ptr(), fx.numel() * 2
-                ops.gemm_fused(None, Lw["qkv_w"], qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag, M=B)
+                ops.gemm_fused(None, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag, M=B)
             else:
-                fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=ss_d, ss_ld=tiles, ss_n=n_ss, eps=1e-6, **rope)
-                ops.gemm_fused(xq, Lw["qkv_w"], qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag, M=B)
-            if merge_in_gemv:
-                ops.attention(qb, nh * hd, None, nh * hd, cache.k[i], cache.Smax * kvd, hd, kvd,
-                              cache.vt[i], kvd * cache.Smax, hd * cache.Smax, cache.Smax,
-                              B=B, Lq=1, Lkv=1, lkv_dev=st["kv_len"], Hq=nh, Hkv=nkv, D=hd,
-                              scale=1.0 / math.sqrt(hd), split_keys=SK, nsplit=nsplit, part_o=part_o,
-                              part_ml=part_ml, kcap=cache.Smax, kd=cache.kd[i], vd=cache.vd[i])
-                if add_o:
-                    fa = ops.fused_args(pro_mode=ops.PRO_ATTN_COMBINE, part_o=part_o, part_ml=part_ml, asplit=nsplit,
-                                        head_dim=hd, dtw=dt, q_per_kv=nh // nkv, kv_heads=nkv, slot_dev=st["kv_len"],
-                                        akeys=SK, resid_in=res if (fx is not None and i == 0) else None,
-                                        status=fx_st)
-                    ops.gemm_fused(None, Lw["o_w"], add_dst, fa, epi=add_epi | w.wflag, M=B, ksplit=so)
+                fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=f.ss_d, ss_ld=tiles, ss_n=f.n_ss, eps=1e-6, **rope)
+                ops.gemm_fused(f.xq, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag, M=B)
+            if not merge_in_gemv:
+                attn = self._decode_attn_merged(i, st, cache, ws)
+                fa = ops.fused_args(norm_w=Lw["post_w"], **fin_o)
+                ops.gemm_fused(attn, Lw["o_w"], part, fa, epi=ops.EPI_F32_FIN | w.wflag, M=B, ksplit=ws.so)
+            else:
+                self._attn_split(i, st, cache, ws)
+                if f.add_o:
+                    fa = ops.fused_args(resid_in=res if (fx is not None and i == 0) else None, status=f.fx_st,
+                                        **self._combine_kw(st, ws))
+                    ops.gemm_fused(None, Lw["o_w"], f.add_dst, fa, epi=f.add_epi | w.wflag, M=B, ksplit=ws.so)
                 else:
-                    fa = ops.fused_args(pro_mode=ops.PRO_ATTN_COMBINE, part_o=part_o, part_ml=part_ml, asplit=nsplit,
-                                        head_dim=hd, dtw=dt, q_per_kv=nh // nkv, kv_heads=nkv, slot_dev=st["kv_len"],
-                                        akeys=SK, fin_cnt=cnt, fin_resid=res, ss_out=ss_o, ss_ld=tiles, fin_x=xq,
-                                        norm_w=Lw["post_w"])
-                    ops.gemm_fused(None, Lw["o_w"], part, fa, epi=ops.EPI_F32_FIN | w.wflag, M=B, ksplit=so)
-            else:
-                self._decode_attn_merged(i, st, cache, qb, attn, part_o, part_ml, SK, nsplit)
-                fa = ops.fused_args(fin_cnt=cnt, fin_resid=res, ss_out=ss_o, ss_ld=tiles, fin_x=xq,
-                                    norm_w=Lw["post_w"])
-                ops.gemm_fused(attn, Lw["o_w"], part, fa, epi=ops.EPI_F32_FIN | w.wflag, M=B, ksplit=so)
-            nxt_w = w.tl[i + 1]["in_w"] if i + 1 < nl else w.final_w
-            self._mlp_fin(Lw, xq, ss_o, tiles, n_ss, h, part, cnt, res, ss_d, nxt_w, B, sd,
-                          add=add_down and i + 1 < nl, gu_rms=add_o, fx=fx, fx_st=fx_st)
-        return xq, ss_d, tiles, n_ss
+                    fa = ops.fused_args(norm_w=Lw["post_w"], **fin_o, **self._combine_kw(st, ws))
+                    ops.gemm_fused(None, Lw["o_w"], part, fa, epi=ops.EPI_F32_FIN | w.wflag, M=B, ksplit=ws.so)
+            self._mlp_fin(i, ws, f)
+        return f.xq, f.ss_d, tiles, f.n_ss
 
-    def _mlp_fin(self, Lw, xq, ss_o, tiles, n_ss, h, part, cnt, res, ss_d, nxt_w, B, sd, add=False, gu_rms=False,
-                 fx=None, fx_st=None):
-        """gate/up + down of a _decode_layers_fin layer: x' = xq with rstd from ss_o -> h -> down, finalised into res
-        (x' of the next norm -> xq, its sums of squares -> ss_d).  add: down adds its partials into res with float
-        atomics (EPI_F32_ADD), or into the fixed-point accumulator fx (EPI_FX_ADD); the next GEMV normalises res (+ fx)
-        itself.  gu_rms: o_proj did so, gate/up normalises res (+ fx).  The finalising form adds fx and clears it."""
+    def _mlp_fin(self, i: int, ws, f):
+        """gate/up + down of layer i of _decode_layers_fin (f: its buffers and flags): x' = f.xq with rstd from f.ss_o
+        -> h -> down, finalised into the residual (x' of the next norm -> f.xq, its sums of squares -> f.ss_d).
+        f.add_down (every layer but the last): down adds its partials into the residual with float atomics
+        (EPI_F32_ADD), or into the fixed-point accumulator f.fx (EPI_FX_ADD); the next GEMV normalises the residual
+        (+ fx) itself.  f.add_o: o_proj did so, gate/up normalises the residual (+ fx).  The finalising form adds fx
+        and clears it."""
         w = self.w
-        if gu_rms:
+        Lw, last = w.tl[i], i + 1 == len(w.tl)
+        B, res, fx = ws.B, ws.res_a, f.fx
+        if f.add_o:
             fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res if fx is None else None, fx=fx, nsplit=0,
                                 norm_w=Lw["post_w"], eps=1e-6)
-            ops.gemm_fused(None, Lw["gu_w"], h, fa, epi=ops.EPI_BF16_GELU_MUL | w.wflag, M=B)
+            ops.gemm_fused(None, Lw["gu_w"], ws.h, fa, epi=ops.EPI_BF16_GELU_MUL | w.wflag, M=B)
         else:
-            fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=ss_o, ss_ld=tiles, ss_n=n_ss, eps=1e-6)
-            ops.gemm_fused(xq, Lw["gu_w"], h, fa, epi=ops.EPI_BF16_GELU_MUL | w.wflag, M=B)
-        if add:
-            if fx is not None:
-                ops.gemm_fused(h, Lw["down_w"], fx, ops.fused_args(status=fx_st), epi=ops.EPI_FX_ADD | w.wflag, M=B,
-                               ksplit=sd)
-            else:
-                ops.gemm_fused(h, Lw["down_w"], res, ops.fused_args(), epi=ops.EPI_F32_ADD | w.wflag, M=B, ksplit=sd)
+            fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=f.ss_o, ss_ld=f.tiles, ss_n=f.n_ss, eps=1e-6)
+            ops.gemm_fused(f.xq, Lw["gu_w"], ws.h, fa, epi=ops.EPI_BF16_GELU_MUL | w.wflag, M=B)
+        if f.add_down and not last:
+            ops.gemm_fused(ws.h, Lw["down_w"], f.add_dst, ops.fused_args(status=f.fx_st), epi=f.add_epi | w.wflag,
+                           M=B, ksplit=ws.sd)
             return
-        fa = ops.fused_args(fin_cnt=cnt, fin_resid=res, ss_out=ss_d, ss_ld=tiles, fin_x=xq, norm_w=nxt_w, fx=fx)
-        ops.gemm_fused(h, Lw["down_w"], part, fa, epi=ops.EPI_F32_FIN | w.wflag, M=B, ksplit=sd)
+        nxt_w = w.final_w if last else w.tl[i + 1]["in_w"]
+        fa = ops.fused_args(fin_cnt=f.cnt, fin_resid=res, ss_out=f.ss_d, ss_ld=f.tiles, fin_x=f.xq, norm_w=nxt_w, fx=fx)
+        ops.gemm_fused(ws.h, Lw["down_w"], ws.part, fa, epi=ops.EPI_F32_FIN | w.wflag, M=B, ksplit=ws.sd)
 
     def _split_keys(self, B: int, Smax: int) -> int:
         """Keys per decode-attention split: 32 (one MFMA block) at small batch; at B > FUSE_MAX_B (separate
@@ -918,40 +915,19 @@ class PaliGemmaEngine:
         if B <= self.FUSE_MAX_B:
             return self.DECODE_SPLIT_KEYS_SMALL
         blocks = (Smax + SK - 1) // SK
-        if self.DECODE_ONE_ROUND and B * blocks >= 2048:
-            # long KV x batch: 4-wave splits of several 32-key rounds per wave, about 512 workgroups in all (two
-            # resident per CU: one round) -- pt-896 x32: 12 splits of 384 keys instead of 36 of 128 (2.25 rounds)
-            per_batch = max(4, (512 // B) // 4 * 4)
-            return 128 * (-(-Smax // (128 * per_batch)))
         mult = max(1, min(8, (B * blocks) // self.DECODE_SPLIT_TARGET))
         # a power of two: 2 / 4 / 8-block splits run one wave per block, merged in LDS (attn_decode_wg_kernel)
         return SK * (1 << (mult.bit_length() - 1))
 
-    def _decode_layers_unfused(self, st, cache, res, xn, qb, h, part, part_o, part_ml, nsplit, dt, cos_t, sin_t,
-                               SK=None):
+    def _decode_layers_unfused(self, st: dict, cache: KVStore, ws) -> int:
         """Decode layers for B > FUSE_MAX_B: the RMSNorm and the split-KV merge run once as their own
-        kernels (fused into every GEMV workgroup they would be recomputed B-fold per workgroup)."""
+        kernels (fused into every GEMV workgroup they would be recomputed B-fold per workgroup).  17..32 fp8 rows run
+        on the fp8 GEMVs, with MX h / MX norms where _mx_decode allows.  Returns the slab count the final norm must
+        add."""
         w = self.w
-        B = st["ids"].numel()
-        nh, nkv, hd = w.heads, w.kv_heads, w.head_dim
-        kvd = nkv * hd
-        so, sd = self.split_o, self.split_down
-        attn = self._buf("d_attn", (B, nh * hd), torch.bfloat16)
-        # 17..32 rows on the fp8 GEMV, one rank: o_proj / down_proj may add their partials into the residual with
-        # float atomics (no slabs for the next norm to re-read), as the batch-1 path does.  Measured slower at pt-896
-        # x32 (down 11.5 -> 14.9 us: the MFMA output layout scatters each atomic instruction over 16 rows), so off
-        add = (self.tp == 1 and self.DECODE_ADD_B32 and self.FP8_GEMV and self._fp8_rows(B) and B <= 32
-               and "o_w8f" in w.tl[0] and "down_w8f" in w.tl[0])
-        # 17..32 rows on the fp8 GEMVs: the gate/up epilogue max-es each row's |h| (amax_out) and the down GEMV
-        # quantises h while staging it (ops.gemm8_hx) -- no quantiser launch; the QKV GEMV clears the maxima
-        ich = h.shape[1] // 128
-        sdh = ich // self.HQ_CHUNKS                # the down GEMV's splits on this path (x chunk per workgroup)
-        hq = (self.HQ_FUSED and self.FP8_GEMV and self._fp8_rows(B) and B <= 32 and not add
-              and all(k in w.tl[0] for k in ("qkv_w8f", "gu_w8f", "down_w8f"))
-              and ich % self.HQ_CHUNKS == 0 and part.shape[0] >= sdh)
-        I, H = h.shape[1], w.hidden
+        B, res, part, h = ws.B, ws.res_a, ws.part, ws.h
+        I, H = w.inter, w.hidden
         mx, mxn = self._mx_decode(B)
-        mx, mxn = mx and not hq and not add, mxn and not hq and not add
         if mx:
             h8 = self._buf("d_h8", (B, I), torch.uint8)
             hs = self._buf("d_hs", (B * I // 32,), torch.uint8)
@@ -959,59 +935,37 @@ class PaliGemmaEngine:
             x8n = self._buf("d_x8n", (B, H), torch.uint8)
             xsn = self._buf("d_xsn", (B * H // 32,), torch.uint8)
             ssn = self._buf("d_ssn", (B, H // 1024), torch.float32)
-        if hq:
-            amax = self._buf("d_hamax", (B * self.AMAX_LD,), torch.int32)
-            fa_gu = ops.fused_args(amax_out=amax, amax_ld=self.AMAX_LD)
         ns = 0
         for i, Lw in enumerate(w.tl):
-            fa = ops.fused_args(head_dim=hd, cos_t=cos_t, sin_t=sin_t, pos=st["pos"], rows_per_batch=1,
-                                slot_dev=st["kv_len"], slot_base=0, kc=cache.k[i], vtc=cache.vt[i], smax=cache.Smax,
-                                q_heads=nh, kv_heads=nkv, kd=cache.kd[i], vd=cache.vd[i])
+            fa = ops.fused_args(**self._rope_kw(i, st, cache, ws))
             if mxn:                                 # MX rows of x*(1+w); the q|k|v GEMV applies rstd
                 ops.norm_residual_mx(res, Lw["in_w"], x8n, xsn, ssn, partials=part, nsplit=ns)
-                ops.gemm8(x8n, None, Lw["qkv_w8f"], Lw["qkv_s8"], qb, epi=ops.EPI_QKV_ROPE, M=B, fa=fa, frag=True,
+                ops.gemm8(x8n, None, Lw["qkv_w8f"], Lw["qkv_s8"], ws.qb, epi=ops.EPI_QKV_ROPE, M=B, fa=fa, frag=True,
                           mx_in=xsn, ss_in=ssn)
             else:
-                xin = self._norm(res, Lw["in_w"], part, ns, xn, B)
-                if hq:
-                    fa.amax_zero, fa.amax_zero_n = amax.data_ptr(), B * self.AMAX_LD
-                self._lin(xin, Lw, "qkv", qb, ops.EPI_QKV_ROPE, B, fa=fa)
-            a8 = self._decode_attn_merged(i, st, cache, qb, attn, part_o, part_ml, SK or self.DECODE_SPLIT_KEYS,
-                                          nsplit, want_fp8=self._fp8_rows(B))
-            if add:
-                self._lin(a8 or attn, Lw, "o", res, ops.EPI_F32_ADD, B, ksplit=so)
-                n_o = 0
-            else:
-                self._lin(a8 or attn, Lw, "o", part, ops.EPI_F32, B, ksplit=so)
-                n_o = self._allreduce_slabs(part, so)
-            if mxn:                                 # MX norm -> gate/up (rstd, MX h) -> down (MX rows)
+                xin = self._norm(res, Lw["in_w"], part, ns, ws.xn, B)
+                self._lin(xin, Lw, "qkv", ws.qb, ops.EPI_QKV_ROPE, B, fa=fa)
+            attn = self._decode_attn_merged(i, st, cache, ws, want_fp8=self._fp8_rows(B))
+            self._lin(attn, Lw, "o", part, ops.EPI_F32, B, ksplit=ws.so)
+            n_o = self._allreduce_slabs(part, ws.so)
+            if mxn:                                 # MX norm -> gate/up (rstd, MX h)
                 ops.norm_residual_mx(res, Lw["post_w"], x8n, xsn, ssn, partials=part, nsplit=n_o)
                 ops.gemm8(x8n, None, Lw["gu_w8f"], Lw["gu_s8"], h8, epi=ops.EPI_BF16_GELU_MUL, M=B, frag=True,
                           mx_in=xsn, ss_in=ssn, mx_out=hs)
-                ops.gemm8(h8, None, Lw["down_w8f"], Lw["down_s8"], part, epi=ops.EPI_F32, M=B, ksplit=sd, frag=True,
-                          mx_in=hs)
-                ns = self._allreduce_slabs(part, sd)
-                continue
-            xin = self._norm(res, Lw["post_w"], part, n_o, xn, B)
-            if hq:
-                self._lin(xin, Lw, "gu", h, ops.EPI_BF16_GELU_MUL, B, fa=fa_gu)
-                ops.gemm8_hx(h, amax, self.AMAX_LD, Lw["down_w8f"], Lw["down_s8"], part, M=B, ksplit=sdh)
-                ns = self._allreduce_slabs(part, sdh)
-                continue
-            if mx:                                  # MX h: e4m3 + block scales straight from gate/up into down
-                x8, xs = xin
-                ops.gemm8(x8, xs, Lw["gu_w8f"], Lw["gu_s8"], h8, epi=ops.EPI_BF16_GELU_MUL, M=B, frag=True, mx_out=hs)
-                ops.gemm8(h8, None, Lw["down_w8f"], Lw["down_s8"], part, epi=ops.EPI_F32, M=B, ksplit=sd, frag=True,
-                          mx_in=hs)
-                ns = self._allreduce_slabs(part, sd)
-                continue
-            self._lin(xin, Lw, "gu", h, ops.EPI_BF16_GELU_MUL, B)
-            if add:
-                self._lin(h, Lw, "down", res, ops.EPI_F32_ADD, B, ksplit=sd)
-                ns = 0
             else:
-                self._lin(h, Lw, "down", part, ops.EPI_F32, B, ksplit=sd)
-                ns = self._allreduce_slabs(part, sd)
+                xin = self._norm(res, Lw["post_w"], part, n_o, ws.xn, B)
+                if mx:                              # fp8 rows -> gate/up writing MX h: e4m3 + block scales
+                    x8, xs = xin
+                    ops.gemm8(x8, xs, Lw["gu_w8f"], Lw["gu_s8"], h8, epi=ops.EPI_BF16_GELU_MUL, M=B, frag=True,
+                              mx_out=hs)
+                else:
+                    self._lin(xin, Lw, "gu", h, ops.EPI_BF16_GELU_MUL, B)
+            if mx:                                  # MX h straight from gate/up into down
+                ops.gemm8(h8, None, Lw["down_w8f"], Lw["down_s8"], part, epi=ops.EPI_F32, M=B, ksplit=ws.sd,
+                          frag=True, mx_in=hs)
+            else:
+                self._lin(h, Lw, "down", part, ops.EPI_F32, B, ksplit=ws.sd)
+            ns = self._allreduce_slabs(part, ws.sd)
         return ns
 
     def sample(self, logits: torch.Tensor, st: dict, sampler: dict, advance: bool,
@@ -1025,9 +979,7 @@ class PaliGemmaEngine:
             w = self.w
             B = st["ids"].numel()
             ops.argmax_embed(logits, st["ids"], st["ws"], w.embed, feats, feats.shape[0] if feats is not None else 0,
-                             self._buf("d_res_a", (B, w.hidden), torch.float32), image_id=self.image_token_id,
-                             pad_id=self.pad_id, img_scale=float(w.proj_dim ** -0.5),
-                             normalizer=float(w.hidden ** 0.5), **kw)
+                             self._buf("d_res_a", (B, w.hidden), torch.float32), **self._embed_kw(), **kw)
         elif sampler.get("do_sample"):
             ops.topp_sample(logits, st["ids"], sampler["uniforms"], temperature=sampler["temperature"],
                             top_p=sampler["top_p"], **kw)

@@ -301,6 +301,45 @@ def test_engine_refuses_split_knobs_the_kernels_reject(monkeypatch):
         engine.PaliGemmaEngine(cfg, P, device="cpu")
 
 
+def test_decode_route_and_split_tables(monkeypatch):
+    """Which of the three decode layer forms runs for a batch size (engine._decode_route), and the o_proj / down_proj
+    split-K it runs with (engine._decode_splits): the table the decode step is built on, pinned without a device."""
+    from types import SimpleNamespace
+    from pghip import configs, engine, weights
+    cfg = configs.TINY
+    W = synth.generate_state_dict(cfg)
+    for k in ("PG_SPLIT_O", "PG_SPLIT_DOWN"):
+        monkeypatch.delenv(k, raising=False)
+
+    def pack(**kw):
+        return weights.PackedWeights(cfg, lambda k: torch.from_numpy(W[k]), device="cpu", **kw)
+
+    def make(P, comm=None):
+        return engine.PaliGemmaEngine(cfg, P, device="cpu", comm=comm)
+
+    def routes(eng, Bs):
+        return {B: eng._decode_route(B) for B in Bs}
+
+    bf16 = pack()
+    eng = make(bf16)
+    assert routes(eng, (1, 2, 3, 4, 5, 16, 17, 32)) == {1: "fin", 2: "fin", 3: "unfused", 4: "unfused", 5: "fin",
+                                                        16: "fin", 17: "unfused", 32: "unfused"}
+    splits = {B: eng._decode_splits(B, eng._decode_route(B)) for B in (1, 8, 20)}
+    assert splits == {1: (2, 8), 8: (1, 4), 20: (2, 8)}
+    eng.USE_FIN = False                             # (knobs are class attributes an instance may override)
+    assert routes(eng, (1, 8)) == {1: "fused", 8: "unfused"}
+    eng = make(bf16)
+    eng.FUSE_MAX_B = 0
+    assert routes(eng, (1,)) == {1: "unfused"}
+    assert routes(make(pack(fp8=True)), (16, 17)) == {16: "fin", 17: "unfused"}
+    two = SimpleNamespace(rank=0, world=2, backend="none", capturable=False)
+    assert routes(make(pack(tp_rank=0, tp_world=2), comm=two), (1, 8)) == {1: "fused", 8: "unfused"}
+    monkeypatch.setenv("PG_SPLIT_DOWN", "2")        # an override holds on every route
+    eng = make(bf16)
+    assert [eng._decode_splits(B, eng._decode_route(B)) for B in (1, 3, 8, 16, 20)] == [(2, 2), (2, 2), (1, 2), (1, 2),
+                                                                                       (2, 2)]
+
+
 def test_bench_refuses_world_size_other_than_gpus():
     """bench.py under a launcher whose WORLD_SIZE differs from --gpus fails loudly before touching the device (the
     driver's N-GPU line must come from N ranks)."""

@@ -112,8 +112,8 @@ def test_slab_sum_into_strided_rows():
 @pytest.mark.parametrize("M,N,K,epi,s", [(300, 300, 128, "gelu", 1), (300, 300, 128, "f32", 2),
                                          (16384, 1152, 1152, "f32", 1), (16384, 4304, 1152, "gelu", 1)])
 def test_gemm_column_blocks(M, N, K, epi, s):
-    """engine._gemm_cols: whole 256-column tiles + the ragged remaining columns as two GEMMs on column views
-    of one output (bias sliced, slabs keep their stride) equal the one-launch GEMM."""
+    """ops.gemm on column views: whole 256-column tiles + the ragged remaining columns as two GEMMs into one
+    output (bias sliced, slabs keep their stride) equal the one-launch GEMM."""
     from pghip import ops
     A, W = rnd(M, K, seed=33), rnd(N, K, scale=1 / math.sqrt(K), seed=34)
     bias = torch.randn(N).cuda() * 0.1
