@@ -23,7 +23,8 @@ extern "C" {
 #endif
 
 int pg_abi_version(void);   /* 13: PG_EPI_F32_RES (the prefill residual add in the producing tile GEMM), pg_attn_probs
-                              (the modules' attention weights); 12: PgFusedArgs.status (FX_ADD range check), amax_zero on the bf16 GEMV, the xGMI
+                              (the modules' attention weights), and, added later under the same number (purely additive),
+                              pg_image_preprocess_modes + pg_image_palette; 12: PgFusedArgs.status (FX_ADD range check), amax_zero on the bf16 GEMV, the xGMI
                               reduce-scatter + all-gather (pg_allreduce_xgmi_rs) and err diagnostics; 11: PgFusedArgs mx_out / mx_in (MX block-scaled fp8 decode MLP rows); 10: PG_EPI_FX_ADD + PgFusedArgs.fx (bit-reproducible decode residual); 9: PgFusedArgs amax_out / amax_in (pro_mode 5) / amax_zero, PG_ATTN_PIPE; 8: pg_allreduce_xgmi_slabs, PG_EPI_F32_ADD; 7: pg_attn_decode's optional fp8 row copy (q8 / q8_scale / q8_ld); 6: decode-order KV copies (PgFusedArgs.kd / vd; pg_attention, pg_attn_decode read
                               them); 5: pg_attn_decode; 4: the measured-slower decode variants removed */
 /* sha256 (hex, 64 chars + NUL) of the csrc/ sources, include/pghip.h and the compile flags this library was built
@@ -274,6 +275,23 @@ int pg_topp_sample(const float* logits, long ld, int B, int V, float temperature
 int pg_image_preprocess(const uint8_t* src, int H, int W, int S, const int* hb, const int* hk, int hks,
                         const int* vb, const int* vk, int vks, int y0, int rows, const float* lut, uint8_t* tmp,
                         float* out, hipStream_t stream);
+/* (added under ABI 13; the version stays 13, nothing existing changed)  pg_image_preprocess for the other 8-bit modes
+ * PIL resamples: src uint8 [H][W][C] interleaved, C = 1 (L), 2 (LA), 3 (RGB) or 4 (RGBA).  alpha != 0 (C 2 or 4 only):
+ * the last channel is an alpha, and the resize runs as PIL's does -- colour bytes premultiplied ((c*a + 128) folded
+ * as MULDIV255), every channel through the same passes, then un-premultiplied (a in {0, 255}: unchanged, else
+ * min(255, 255*c / a)); with no pass to run (H == W == S) PIL copies, and so does this.  convert("RGB") follows:
+ * alpha dropped without compositing, a grey channel written three times.  alpha == 0 with C 2 or 4 ignores the last
+ * channel.  Tables, y0 / rows, lut and out as pg_image_preprocess; tmp uint8 [rows][S][C]; y0 + rows <= H always;
+ * src and tmp aligned to the pixel when C is 2 or 4. */
+int pg_image_preprocess_modes(const uint8_t* src, int H, int W, int C, int alpha, int S, const int* hb,
+                              const int* hk, int hks, const int* vb, const int* vk, int vks, int y0, int rows,
+                              const float* lut, uint8_t* tmp, float* out, hipStream_t stream);
+/* (added under ABI 13)  P and 1 images, which PIL resizes NEAREST whatever filter is asked for: out[c][y][x] =
+ * pal_lut[src[ytab[y]][xtab[x]]][c].  src uint8 [H][W] palette indices (mode 1: 0 / 1), xtab / ytab int32 [S] source
+ * column / row per output (pghip/image.py nearest_index; an entry outside the image reads index 0), pal_lut float32
+ * [256][3] the palette composed with the normalise table (pghip/image.py palette_lut). */
+int pg_image_palette(const uint8_t* src, int H, int W, int S, const int* xtab, const int* ytab,
+                     const float* pal_lut, float* out, hipStream_t stream);
 
 /* name-seeded synthetic weights, bit-identical to oracle/synth.py (out_kind 0 bf16, 1 f32). */
 int pg_synth_fill(void* out, long n, unsigned int seedmix, float a, float mean, int out_kind,

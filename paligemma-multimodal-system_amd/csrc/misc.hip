@@ -674,3 +674,206 @@ extern "C" int pg_image_preprocess(const uint8_t* src, int H, int W, int S, cons
   PG_LAUNCH_CHECK();
   return 0;
 }
+
+// ---------------------------------------------------------------- image modes (L, LA, RGB, RGBA; P and 1 below)
+// The same two passes for C = 1..4 interleaved channels, one thread per output PIXEL with C accumulators, because
+// PIL resizes LA / RGBA premultiplied (Image.resize: convert to La / RGBa, resample every band, convert back) and the
+// un-premultiply needs the pixel's own alpha.  Premultiply (Convert.c rgbA2rgba, MULDIV255) rides on the loads of
+// whichever pass runs first; un-premultiply (rgba2rgbA), the alpha drop, the L -> RGB replication of convert("RGB"),
+// the normalise table and the CHW store are the epilogue of the vertical kernel, which always runs last.
+// clip8_22 with the clamp ahead of the shift (the same byte for every acc).  The pixel kernels pack these bytes into
+// one word; hipcc (ROCm 7.2) selects a pair of shift-then-clamp bytes to v_ashr_pk_u8_i32 and takes the upper half
+// of its destination for zero, but the MI355X leaves stale bits there, which the word store then puts into the third
+// and fourth channel.  This form is not matched (no v_ashr_pk in the .s).
+__device__ __forceinline__ int clip8_22_px(int acc) {
+  const int hi = (256 << 22) - 1;
+  return (int)((uint32_t)(acc < 0 ? 0 : (acc > hi ? hi : acc)) >> 22);
+}
+
+template <int C>
+__device__ __forceinline__ void load_px(const uint8_t* __restrict__ p, int (&v)[C]) {
+  if constexpr (C == 4) {
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
+    v[0] = (int)(w & 255u), v[1] = (int)((w >> 8) & 255u), v[2] = (int)((w >> 16) & 255u), v[3] = (int)(w >> 24);
+  } else if constexpr (C == 2) {
+    const uint32_t w = *reinterpret_cast<const uint16_t*>(p);
+    v[0] = (int)(w & 255u), v[1] = (int)(w >> 8);
+  } else {
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = p[c];
+  }
+}
+
+template <int C>
+__device__ __forceinline__ void store_px(uint8_t* __restrict__ p, const int (&v)[C]) {
+  if constexpr (C == 4) {
+    *reinterpret_cast<uint32_t*>(p) =
+        (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+  } else if constexpr (C == 2) {
+    *reinterpret_cast<uint16_t*>(p) = (uint16_t)(v[0] | (v[1] << 8));
+  } else {
+#pragma unroll
+    for (int c = 0; c < C; ++c) p[c] = (uint8_t)v[c];
+  }
+}
+
+// colour bytes * alpha / 255, rounded as PIL's MULDIV255; the alpha byte (last channel) passes through
+template <int C>
+__device__ __forceinline__ void premultiply_px(int (&v)[C]) {
+#pragma unroll
+  for (int c = 0; c < C - 1; ++c) {
+    const int t = v[c] * v[C - 1] + 128;
+    v[c] = ((t >> 8) + t) >> 8;
+  }
+}
+
+// pass 1: tmp[r][xx][:] = clip8(2^21 + sum_x premul(src[y0 + r][xmin + x][:]) * hk[xx][x]); premultiplied when ALPHA
+template <int C, bool ALPHA>
+__global__ __launch_bounds__(256) void resize_h_px_kernel(const uint8_t* __restrict__ src, int W, int y0, int rows,
+                                                          int S, const int* __restrict__ hb,
+                                                          const int* __restrict__ hk, int hks,
+                                                          uint8_t* __restrict__ tmp) {
+  const long total = (long)rows * S;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int xx = (int)(i % S);
+    const long r = i / S;
+    const int xmin = hb[2 * xx], n = hb[2 * xx + 1];
+    const int* k = hk + (long)xx * hks;
+    const uint8_t* p = src + ((long)(y0 + r) * W + xmin) * C;
+    int acc[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] = 1 << 21;
+    for (int x = 0; x < n; ++x) {
+      int v[C];
+      load_px<C>(p + (long)x * C, v);
+      if constexpr (ALPHA) premultiply_px<C>(v);
+      const int kx = k[x];
+#pragma unroll
+      for (int c = 0; c < C; ++c) acc[c] += v[c] * kx;
+    }
+    int o[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = clip8_22_px(acc[c]);
+    store_px<C>(tmp + i * C, o);
+  }
+}
+
+// pass 2: the vertical pass over in (the source when premul, else pass 1's premultiplied output), or a plain read when
+// vb == null; then, when ALPHA, c = a in {0, 255} ? c : min(255, 255 * c / a); then out[ch][yy][xx] = lut[colour ch]
+// (1 or 2 channels: the grey byte three times; 3 or 4: r, g, b -- a last channel that is no alpha is dropped unread).
+template <int C, bool ALPHA>
+__global__ __launch_bounds__(256) void resize_v_px_kernel(const uint8_t* __restrict__ in, int Win, int yshift, int S,
+                                                          const int* __restrict__ vb, const int* __restrict__ vk,
+                                                          int vks, int premul, const float* __restrict__ lut,
+                                                          float* __restrict__ out) {
+  const long total = (long)S * S;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int xx = (int)(i % S), yy = (int)(i / S);
+    int v[C];
+    if (vb) {
+      const int ymin = vb[2 * yy] - yshift, n = vb[2 * yy + 1];
+      const int* k = vk + (long)yy * vks;
+      const uint8_t* p = in + ((long)ymin * Win + xx) * C;
+      int acc[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) acc[c] = 1 << 21;
+      for (int y = 0; y < n; ++y) {
+        load_px<C>(p + (long)y * Win * C, v);
+        if constexpr (ALPHA) {
+          if (premul) premultiply_px<C>(v);
+        }
+        const int ky = k[y];
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] += v[c] * ky;
+      }
+#pragma unroll
+      for (int c = 0; c < C; ++c) v[c] = clip8_22_px(acc[c]);
+    } else {
+      load_px<C>(in + ((long)yy * Win + xx) * C, v);
+    }
+    if constexpr (ALPHA) {
+      const int a = v[C - 1];
+      if (a != 0 && a != 255) {
+#pragma unroll
+        for (int c = 0; c < C - 1; ++c) v[c] = min(255, 255 * v[c] / a);
+      }
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) out[(long)ch * total + i] = lut[v[C <= 2 ? 0 : ch]];
+  }
+}
+
+template <int C, bool ALPHA>
+static int launch_resize_px(const uint8_t* src, int W, int S, const int* hb, const int* hk, int hks, const int* vb,
+                            const int* vk, int vks, int y0, int rows, const float* lut, uint8_t* tmp, float* out,
+                            hipStream_t stream) {
+  const uint8_t* in = src;
+  int win = W, yshift = 0;
+  if (hb) {
+    const long n = (long)rows * S;
+    hipLaunchKernelGGL((resize_h_px_kernel<C, ALPHA>), dim3((int)min((n + 255) / 256, 4096L)), dim3(256), 0, stream,
+                       src, W, y0, rows, S, hb, hk, hks, tmp);
+    in = tmp;
+    win = S;
+    yshift = y0;
+  }
+  const long n = (long)S * S;
+  hipLaunchKernelGGL((resize_v_px_kernel<C, ALPHA>), dim3((int)min((n + 255) / 256, 4096L)), dim3(256), 0, stream, in,
+                     win, yshift, S, vb, vk, vks, hb ? 0 : 1, lut, out);
+  PG_LAUNCH_CHECK();
+  return 0;
+}
+
+// (added under ABI 13) pg_image_preprocess for C interleaved uint8 channels: 1 = L, 2 = LA, 3 = RGB, 4 = RGBA.
+// alpha: the last channel is an alpha PIL premultiplies by while it resizes.  With no pass to run (H == W == S) PIL
+// copies the image, so the alpha channel is only dropped, as it is when alpha == 0.
+extern "C" int pg_image_preprocess_modes(const uint8_t* src, int H, int W, int C, int alpha, int S, const int* hb,
+                                         const int* hk, int hks, const int* vb, const int* vk, int vks, int y0,
+                                         int rows, const float* lut, uint8_t* tmp, float* out, hipStream_t stream) {
+  PG_REQUIRE(H > 0 && W > 0 && S > 0 && lut && out && src);
+  PG_REQUIRE(C >= 1 && C <= 4 && (!alpha || C == 2 || C == 4));
+  PG_REQUIRE(rows > 0 && y0 >= 0 && y0 <= H - rows);
+  PG_REQUIRE(hb ? (hk && hks > 0 && tmp) : W == S);
+  PG_REQUIRE(vb ? (vk && vks > 0) : (hb ? rows == S : H == S));
+  // whole-pixel loads and stores: 32-bit for C = 4, 16-bit for C = 2
+  const uintptr_t amask = C == 4 ? 3 : (C == 2 ? 1 : 0);
+  PG_REQUIRE((((uintptr_t)src | (uintptr_t)tmp) & amask) == 0);
+  const bool a = alpha && (hb || vb);
+#define PG_PX(c, al) \
+  return launch_resize_px<c, al>(src, W, S, hb, hk, hks, vb, vk, vks, y0, rows, lut, tmp, out, stream)
+  switch (C) {
+    case 1: PG_PX(1, false);
+    case 2: if (a) PG_PX(2, true); PG_PX(2, false);
+    case 3: PG_PX(3, false);
+    default: if (a) PG_PX(4, true); PG_PX(4, false);
+  }
+#undef PG_PX
+}
+
+// P and 1 images: PIL resizes them NEAREST whatever filter was asked for, and convert("RGB") is a palette lookup.
+// out[ch][y][x] = pal_lut[src[ytab[y]][xtab[x]]][ch]; xtab / ytab int32 [S] (pghip/image.py nearest_index), pal_lut
+// float32 [256][3] the palette composed with the normalise table.  A table entry outside the image reads index 0
+// (PIL leaves such an output pixel cleared); the host asserts there is none.
+__global__ __launch_bounds__(256) void palette_kernel(const uint8_t* __restrict__ src, int H, int W, int S,
+                                                      const int* __restrict__ xtab, const int* __restrict__ ytab,
+                                                      const float* __restrict__ pal, float* __restrict__ out) {
+  const long total = (long)S * S;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int sx = xtab[i % S], sy = ytab[i / S];
+    const bool inside = (unsigned)sx < (unsigned)W && (unsigned)sy < (unsigned)H;
+    const int idx = inside ? src[(long)sy * W + sx] : 0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) out[(long)ch * total + i] = pal[idx * 3 + ch];
+  }
+}
+
+// (added under ABI 13)
+extern "C" int pg_image_palette(const uint8_t* src, int H, int W, int S, const int* xtab, const int* ytab,
+                                const float* pal_lut, float* out, hipStream_t stream) {
+  PG_REQUIRE(H > 0 && W > 0 && S > 0 && src && xtab && ytab && pal_lut && out);
+  const long n = (long)S * S;
+  hipLaunchKernelGGL(palette_kernel, dim3((int)min((n + 255) / 256, 4096L)), dim3(256), 0, stream, src, H, W, S,
+                     xtab, ytab, pal_lut, out);
+  PG_LAUNCH_CHECK();
+  return 0;
+}

@@ -72,9 +72,11 @@ def main(model_path: str = None, prompt: str = None, image_file_path: str = None
     print("Loading model")
     model, tokenizer = load_hf_model(model_path, device)
     model = model.to(device).eval()
+    # resize + normalise on the device, bit-exact with PIL, for RGB, RGBA (the sample pic1.png), LA, L, P and 1 inputs;
+    # any other mode takes the processor's host path
     processor = PaliGemmaProcessor(tokenizer, model.config.vision_config.num_image_tokens or
                                    model.config.text_config.num_image_tokens, model.config.vision_config.image_size,
-                                   device=device)        # resize + normalise on the device (bit-exact with PIL)
+                                   device=device)
     print("Running inference")
     with torch.no_grad():
         test_inference(model, processor, device, prompt, image_file_path, max_tokens_to_generate, temperature,

@@ -57,6 +57,8 @@ SIGNATURES = {
     "pg_argmax_merge": [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp],
     "pg_topp_sample": [vp, i64, i32, i32, f32, f32, vp, vp, vp, i32, vp, vp, vp, vp, vp],
     "pg_image_preprocess": [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+    "pg_image_preprocess_modes": [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+    "pg_image_palette": [vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "pg_synth_fill": [vp, i64, u32, f32, f32, i32, vp],
     "pg_quant_fp8": [vp, i32, i32, i32, vp, i32, vp, vp],
     "pg_norm_residual_fp8": [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, f32, i32, vp],

@@ -463,6 +463,22 @@ def image_preprocess(src, H, W, S, hb, hk, hks, vb, vk, vks, y0, rows, lut, tmp,
               _p(tmp), _p(out), _s())
 
 
+def image_preprocess_modes(src, H, W, C, alpha, S, hb, hk, hks, vb, vk, vks, y0, rows, lut, tmp, out):
+    """pg_image_preprocess for C = 1..4 interleaved channels (L, LA, RGB, RGBA); alpha: resize premultiplied as PIL
+    does.  The boundary rejects what it cannot run (PgHipError)."""
+    _chk(src, torch.uint8, "image")
+    _chk(out, torch.float32, "pixel_values")
+    _lib.call("pg_image_preprocess_modes", _p(src), H, W, C, int(bool(alpha)), S, _p(hb), _p(hk), hks, _p(vb), _p(vk),
+              vks, y0, rows, _p(lut), _p(tmp), _p(out), _s())
+
+
+def image_palette(src, H, W, S, xtab, ytab, pal_lut, out):
+    """out[c][y][x] = pal_lut[src[ytab[y]][xtab[x]]][c]: the NEAREST resize + palette lookup of P and 1 images."""
+    _chk(src, torch.uint8, "image")
+    _chk(out, torch.float32, "pixel_values")
+    _lib.call("pg_image_palette", _p(src), H, W, S, _p(xtab), _p(ytab), _p(pal_lut), _p(out), _s())
+
+
 def synth_fill(out: torch.Tensor, seedmix: int, a: float, mean: float):
     kind = 0 if out.dtype == torch.bfloat16 else 1
     if kind == 1:

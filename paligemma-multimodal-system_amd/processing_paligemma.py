@@ -53,8 +53,9 @@ class PaliGemmaProcessor:
     IMAGE_TOKEN = "<image>"
 
     def __init__(self, tokenizer, num_image_tokens: int, image_size: int, device=None):
-        """device: when a HIP device is given, RGB images are resized/normalised there (pghip.image,
-        bit-exact with the host path below); None keeps the reference's host (PIL + numpy) path."""
+        """device: when a HIP device is given, images of the modes in pghip.image.SUPPORTED_MODES (RGB, RGBA, LA,
+        L, P, 1) are resized/normalised there (bit-exact with the host path below) and any other mode (CMYK, I, F, ...)
+        takes the host path; None keeps the reference's host (PIL + numpy) path for every image."""
         self.device = device
         self.tokenizer = tokenizer
         self.image_seq_len = num_image_tokens
@@ -70,8 +71,10 @@ class PaliGemmaProcessor:
         assert len(images) == 1 and len(text) == 1, \
             "Working with only 1 image and prompt, to test, got more than one"
         from PIL import Image
-        if self.device is not None and all(getattr(im, "mode", None) == "RGB" for im in images):
+        gpu_image = None
+        if self.device is not None:
             from pghip import image as gpu_image
+        if gpu_image is not None and all(getattr(im, "mode", None) in gpu_image.SUPPORTED_MODES for im in images):
             pixel_values = gpu_image.preprocess(images, self.image_size, self.device)
         else:
             pixel_values = torch.tensor(np.stack(process_images(images, self.image_size, scale_factor=1 / 255.0,
