@@ -243,7 +243,10 @@ int pg_embed_merge(const int64_t* ids, const int* rank, int n, const void* embed
                    float* out, hipStream_t stream);
 
 /* greedy next token (inference.py:59,68), first index on ties; optional decode-state advance:
- * hist[*step][b] = token (only while *step < hist_rows), pos[b] += 1, *kv_len += 1, *step += 1. */
+ * hist[*step][b] = token (only while *step < hist_rows), pos[b] += 1, *kv_len += 1, *step += 1.
+ * A NaN never wins against a comparable value; a row with no comparable value (all NaN) returns token 0, so no
+ * id outside [0, V) reaches out_ids, hist or (pg_argmax_pairs) pairs; such a shard's pair is (NaN, vocab_offset),
+ * which loses pg_argmax_merge to every shard with a comparable value. */
 int pg_argmax(const float* logits, long ld, int B, int V, void* workspace, int64_t* out_ids,
               int64_t* hist, int hist_rows, int* step, int* pos, int* kv_len, hipStream_t stream);
 /* pg_argmax, then the next decode step's input rows res[b] = pg_embed_merge of the winners (rank = nullptr:

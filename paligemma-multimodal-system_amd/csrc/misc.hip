@@ -198,6 +198,10 @@ extern "C" int pg_rope_kv_write(void* qkv, int ldq, const int* pos, int T, int L
 __device__ __forceinline__ void am_better(float& bv, int& bi, float v, int i) {
   if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
 }
+// a row (or shard) in which no value compares, i.e. all NaN, leaves the sentinel index: it selects token 0, so no id
+// outside [0, V) leaves these kernels (a NaN among comparable values is simply skipped by am_better)
+#define AM_NONE 0x7FFFFFFF
+__device__ __forceinline__ int am_id(int bi) { return bi == AM_NONE ? 0 : bi; }
 __device__ __forceinline__ void am_block(float& bv, int& bi, float* sv, int* si) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
@@ -221,7 +225,7 @@ __global__ __launch_bounds__(256) void argmax_partial_kernel(const float* __rest
   const int s = ch * per, e = min(V, s + per);
   const float* row = x + (long)b * ld;
   float bv = -INFINITY;
-  int bi = 0x7FFFFFFF;
+  int bi = AM_NONE;
   for (int i = s + threadIdx.x * 4; i < e; i += 1024) {
     if (i + 3 < e) {
       const f32x4 v = *(const f32x4*)(row + i);
@@ -255,6 +259,7 @@ __global__ __launch_bounds__(1024) void argmax_final_kernel(const float* __restr
       am_better(bv, bi, ov, oi);
     }
     if (lane == 0) {
+      bi = am_id(bi);
       out_ids[b] = bi;
       if (hist && st < hist_rows) hist[(long)st * B + b] = bi;   // a step past the history is not recorded
       if (pos) pos[b] += 1;
@@ -296,6 +301,7 @@ __global__ __launch_bounds__(1024) void argmax_final_embed_kernel(const float* _
       am_better(bv, bi, ov, oi);
     }
     if (lane == 0) {
+      bi = am_id(bi);
       win[b] = bi;
       out_ids[b] = bi;
       if (hist && st < hist_rows) hist[(long)st * B + b] = bi;
@@ -333,7 +339,9 @@ __global__ __launch_bounds__(1024) void argmax_pairs_kernel(const float* __restr
       int oi = __shfl_xor(bi, o, 64);
       am_better(bv, bi, ov, oi);
     }
-    if (lane == 0) { pairs[2 * b] = bv; pairs[2 * b + 1] = (float)(bi + vocab_offset); }
+    // a shard with no comparable value reports (NaN, its first index): it loses the merge to every shard that has
+    // one, -inf included, so the merged winner is the single-device winner
+    if (lane == 0) { pairs[2 * b] = bi == AM_NONE ? NAN : bv; pairs[2 * b + 1] = (float)(am_id(bi) + vocab_offset); }
   }
 }
 
@@ -345,8 +353,9 @@ __global__ void argmax_merge_kernel(const float* __restrict__ pairs, int world, 
   const int st = step ? *step : 0;
   for (int b = 0; b < B; ++b) {
     float bv = -INFINITY;
-    int bi = 0x7FFFFFFF;
+    int bi = AM_NONE;
     for (int r = 0; r < world; ++r) am_better(bv, bi, pairs[(r * B + b) * 2], (int)pairs[(r * B + b) * 2 + 1]);
+    bi = am_id(bi);
     out_ids[b] = bi;
     if (hist && st < hist_rows) hist[(long)st * B + b] = bi;
     if (pos) pos[b] += 1;
@@ -503,12 +512,18 @@ __global__ __launch_bounds__(1024) void topp_kernel(const float* __restrict__ lo
   // uniforms and hist hold hist_rows steps: a step past them reuses the last row / is not recorded
   const long srow = step ? (long)min(*step, hist_rows - 1) : 0;
   const float u = uniforms[srow * B + b] * kept;
-  const float lo = scan[tid] - mine;
-  __shared__ int chosen;
-  if (tid == 0) chosen = -1;
+  // The draw belongs to the first thread that holds a kept token and whose inclusive prefix exceeds u; it walks its
+  // chunk from its neighbour's prefix.  (Intervals [scan[tid] - mine, scan[tid]) left gaps: the difference is not
+  // scan[tid - 1] in fp32, and the scan's levels round differently per entry, so even an empty chunk's entry can
+  // exceed its neighbour's; a u inside a gap was claimed by no thread and fell through to the last kept token.)
+  __shared__ int chosen, owner;
+  if (tid == 0) { chosen = -1; owner = 1024; }
   __syncthreads();
-  if (mine > 0.f && u >= lo && u < scan[tid]) {
-    float run = lo;
+  const unsigned long long claims = __ballot(mine > 0.f && u < scan[tid]);
+  if ((tid & 63) == 0 && claims) atomicMin(&owner, tid + __ffsll((long long)claims) - 1);
+  __syncthreads();
+  if (tid == owner) {
+    float run = tid ? scan[tid - 1] : 0.f;
     int pick = -1, last = -1;
     for (int i = s; i < e; ++i) {
       const float v = __expf(x[i] * inv_temp - mx);
@@ -518,7 +533,7 @@ __global__ __launch_bounds__(1024) void topp_kernel(const float* __restrict__ lo
         if (run > u) { pick = i; break; }
       }
     }
-    atomicMax(&chosen, pick >= 0 ? pick : last);
+    chosen = pick >= 0 ? pick : last;
   }
   __syncthreads();
   if (tid == 0) {

@@ -235,15 +235,18 @@ def norm_residual(resid: torch.Tensor, w: torch.Tensor, *, b: Optional[torch.Ten
 
 def norm_residual_fp8(resid: torch.Tensor, w: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, *,
                       b: Optional[torch.Tensor] = None, mode: int = NORM_RMS, eps: float = 1e-6,
-                      partials: Optional[torch.Tensor] = None, nsplit: int = 0, write_resid: bool = True):
+                      partials: Optional[torch.Tensor] = None, nsplit: int = 0, write_resid: bool = True,
+                      row_map: Optional[torch.Tensor] = None):
     """norm_residual with the output quantised to fp8 e4m3 rows (q uint8 [M][H], scale fp32 [M]) for a
-    PG_FP8 GEMM; the bytes equal quant_fp8 of the bf16 output (pg_norm_residual_fp8)."""
+    PG_FP8 GEMM; the bytes equal quant_fp8 of the bf16 output (pg_norm_residual_fp8).  With a row_map, M is its
+    length: q and scale are indexed by the output row, resid and partials by the mapped row."""
     _chk(resid, torch.float32, "resid")
     M, H = resid.shape[-2], resid.shape[-1]
-    if q.dtype != torch.uint8 or q.stride(-1) != 1 or q.shape[-1] < H or scale.numel() < M:
+    M_out = row_map.numel() if row_map is not None else M
+    if q.dtype != torch.uint8 or q.stride(-1) != 1 or q.shape[-1] < H or scale.numel() < M_out:
         raise ValueError("pghip.norm_residual_fp8: bad output buffers")
     _lib.call("pg_norm_residual_fp8", _p(resid), _p(partials), nsplit, M, _p(w), _p(b), _p(q), q.stride(-2),
-              _p(scale), None, M, H, mode, float(eps), int(write_resid), _s())
+              _p(scale), _p(row_map), M_out, H, mode, float(eps), int(write_resid), _s())
     return q, scale
 
 
