@@ -24,7 +24,8 @@ extern "C" {
 
 int pg_abi_version(void);   /* 13: PG_EPI_F32_RES (the prefill residual add in the producing tile GEMM), pg_attn_probs
                               (the modules' attention weights), and, added later under the same number (purely additive),
-                              pg_image_preprocess_modes + pg_image_palette; 12: PgFusedArgs.status (FX_ADD range check), amax_zero on the bf16 GEMV, the xGMI
+                              pg_image_preprocess_modes + pg_image_palette, then pg_attention_rows + pg_attn_decode_rows +
+                              PG_SLOT_ROWS (per-row kv lengths); 12: PgFusedArgs.status (FX_ADD range check), amax_zero on the bf16 GEMV, the xGMI
                               reduce-scatter + all-gather (pg_allreduce_xgmi_rs) and err diagnostics; 11: PgFusedArgs mx_out / mx_in (MX block-scaled fp8 decode MLP rows); 10: PG_EPI_FX_ADD + PgFusedArgs.fx (bit-reproducible decode residual); 9: PgFusedArgs amax_out / amax_in (pro_mode 5) / amax_zero, PG_ATTN_PIPE; 8: pg_allreduce_xgmi_slabs, PG_EPI_F32_ADD; 7: pg_attn_decode's optional fp8 row copy (q8 / q8_scale / q8_ld); 6: decode-order KV copies (PgFusedArgs.kd / vd; pg_attention, pg_attn_decode read
                               them); 5: pg_attn_decode; 4: the measured-slower decode variants removed */
 /* sha256 (hex, 64 chars + NUL) of the csrc/ sources, include/pghip.h and the compile flags this library was built
@@ -165,6 +166,13 @@ typedef struct PgFusedArgs {
  * the workgroups without a K split, for small-M GEMMs whose 64 x 128 grid leaves CUs idle. */
 #define PG_TILE_N64 0x800
 
+/* PG_SLOT_ROWS (added under ABI 13; pg_gemm_fused and pg_gemm_finalize): PgFusedArgs.slot_dev is int32 [B], one word
+ * per batch row, instead of one word for the whole batch -- prompts of different lengths decoded in one batch.
+ * PG_EPI_QKV_ROPE: output row m appends its k / v at slot slot_base + slot_dev[m / rows_per_batch] + m % rows_per_batch.
+ * pro_mode 2 (akeys > 0): row m merges its own ceil((slot_dev[m] + slot_base + 1) / akeys) non-empty splits.  With
+ * slot_dev = the rows' rotary positions and slot_base = -1 both are the row's kv length before this token. */
+#define PG_SLOT_ROWS 0x1000
+
 /* C = A[M][K] . W[N][K]^T with fused epilogue.  nn.Linear call sites: siglip.py:59-62,71-75,156,177-178,
  * 183-185; paligemma.py:57,64; gemma.py:205-207,212-218,255-259,274-278,356,484,523.  K % 32 == 0
  * (% 64 when M > 16), N % 4 == 0.  M <= 16 takes the weight-streaming GEMV path. */
@@ -200,6 +208,18 @@ int pg_attention(const void* q, long q_rs, void* o, long o_rs, const void* k, lo
                  int kcap, const void* kd, const void* vd, hipStream_t stream);
 int pg_attn_combine(const float* part_o, const float* part_ml, int B, int Hq, int Hkv, int D, int nsplit,
                     void* o, long o_rs, hipStream_t stream);
+/* (added under ABI 13; the version stays 13, nothing existing changed)  pg_attention with one kv length per batch row,
+ * lkv_rows int32 [B] in device memory: prompts of different lengths in one batch.  Prefill (split_keys == 0): row b's
+ * queries attend its first lkv_rows[b] keys (1 <= lkv_rows[b] <= Lkv, clamped); Lkv, the most any row holds, picks the
+ * kernel form as for pg_attention and every form takes the per-row count (the flash kernels walk ceil(lkv_rows[b] /
+ * block) key blocks; key splits left without a block write a neutral partial).  Decode (split_keys > 0): row b attends
+ * Lkv + lkv_rows[b] keys.  Rows of K / V^T below Lkv (prefill) or kcap (decode) must hold finite values.  With every
+ * lkv_rows[b] == Lkv (prefill) the output is bit-identical to pg_attention's. */
+int pg_attention_rows(const void* q, long q_rs, void* o, long o_rs, const void* k, long k_bs, long k_hs,
+                      long k_rs, const void* vt, long vt_bs, long vt_hs, long vt_ds, const float* mask,
+                      long mask_bs, long mask_rs, int B, int Lq, int Lkv, const int* lkv_rows, int Hq, int Hkv,
+                      int D, float scale, int split_keys, int nsplit, float* part_o, float* part_ml,
+                      int kcap, const void* kd, const void* vd, hipStream_t stream);
 
 /* The attention weights the reference's modules return, out fp32 [B][Hq][Lq][Lkv] with pg_attention's q / k / mask
  * addressing: probs = 1 softmax(q . k^T * scale + mask) (gemma.py:358), probs = 0 the scaled scores + mask before the
@@ -224,6 +244,12 @@ int pg_attn_decode(const void* q, long q_rs, void* o, long o_rs, const void* kd,
                    const int* lkv_dev, int Hq, int Hkv, int D, float scale, int kcap, int nsplit, int nw, int nb,
                    float* part_o, float* part_ml, int* counters, void* q8, float* q8_scale, long q8_ld,
                    hipStream_t stream);
+/* (added under ABI 13)  pg_attn_decode with one kv length per batch row: row b attends Lkv + lkv_rows[b] keys
+ * (lkv_rows int32 [B], device memory).  The same kernels; with equal lengths the same bits as pg_attn_decode. */
+int pg_attn_decode_rows(const void* q, long q_rs, void* o, long o_rs, const void* kd, const void* vd, int B, int Lkv,
+                        const int* lkv_rows, int Hq, int Hkv, int D, float scale, int kcap, int nsplit, int nw, int nb,
+                        float* part_o, float* part_ml, int* counters, void* q8, float* q8_scale, long q8_ld,
+                        hipStream_t stream);
 
 /* RoPE (gemma.py:112-151) on q in place and k; k -> cache rows, v -> transposed cache (KVCache.update
  * gemma.py:18-57 as a static in-place append). */

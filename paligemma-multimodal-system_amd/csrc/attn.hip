@@ -98,7 +98,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_wg_kernel(AttnArgs a) {
   mfma_fence(o);
   if (NB > 1) {
     const int lkv = __builtin_amdgcn_readfirstlane(
-        __hip_atomic_load(a.lkv_dev ? a.lkv_dev : &pg_zero_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + a.Lkv;
+        __hip_atomic_load(attn_lkv_ptr(a, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + a.Lkv;
     for (int j = 1; j < NB; ++j) {
       const int kb = sp * a.split_keys + (j * NW + wave) * 32;
       if (kb >= lkv) break;                        // wave-uniform: no key of this or a later round is valid
@@ -185,8 +185,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_decode_fused_kernel(AttnArgs 
 #if PG_ATTN_STAMPS
   unsigned long long st0 = __builtin_amdgcn_s_memrealtime(), st1 = 0, st2 = 0, st3 = 0;
 #endif
-  const int lkv_raw =
-      __hip_atomic_load(a.lkv_dev ? a.lkv_dev : &pg_zero_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int lkv_raw = __hip_atomic_load(attn_lkv_ptr(a, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   // the G query rows of this (batch, kv head) in LDS, re-read per block (32 registers fewer: two waves per SIMD)
   // (loaded before the K/V stream, stored to LDS after it is issued: the store waits only for the q loads)
   __shared__ u32x4 sq[16][DP / 8];
@@ -468,7 +467,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
   const int nsg = split ? (int)(gridDim.y / a.Hkv) : 1;
   const int kvh = blockIdx.y / nsg;
   const int sg = blockIdx.y % nsg;
-  const int Lkv = (a.lkv_dev ? *a.lkv_dev : 0) + a.Lkv;
+  const int Lkv = attn_prefill_keys(a, b);
   const int R = a.Lq * a.G;
   const int D = a.D;
 
@@ -631,7 +630,7 @@ __global__ __launch_bounds__(256) void attn_lds_kernel(AttnArgs a) {
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6, c = lane & 15, g = lane >> 4;
   const int b = blockIdx.z, kvh = blockIdx.y;
-  const int Lkv = (a.lkv_dev ? *a.lkv_dev : 0) + a.Lkv;
+  const int Lkv = attn_prefill_keys(a, b);
   const int R = a.Lq * a.G;
   const int D = a.D;
   const int r = (blockIdx.x * 4 + wave) * 16 + c;
@@ -818,7 +817,8 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
   const int lane = t & 63, c = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);   // wave-uniform: scalar branches on the piece counts
   const int b = blockIdx.z, kvh = blockIdx.y;
-  const int Lkv = a.Lkv;
+  // (per-row key counts, pg_attention_rows: row b's workgroups walk ceil(len_b / KB) blocks and mask the tail at len_b)
+  const int Lkv = attn_prefill_keys(a, b);
   const int R = a.Lq * a.G;
   const int D = a.D;
   // key split (a.pf_splits > 1): workgroup x = row tile * nks + split; split ks walks its share of the key blocks
@@ -1261,11 +1261,12 @@ static void launch_fa(int waves, int rpw, bool deep, dim3 grid, hipStream_t stre
 // columns [0, kcap) are readable (a static cache's Smax, a multiple of 32), so each split issues its first block's
 // loads before the kv length arrives from lkv_dev; 0 = rows clamped to the kv length.  Decode with kcap > 0 and
 // D a multiple of 32 reads K and V only from the decode-order copies kd / vd ([B][Hkv][kcap][D], ABI 6).
-extern "C" int pg_attention(const void* q, long q_rs, void* o, long o_rs, const void* k, long k_bs, long k_hs,
-                            long k_rs, const void* vt, long vt_bs, long vt_hs, long vt_ds, const float* mask,
-                            long mask_bs, long mask_rs, int B, int Lq, int Lkv, const int* lkv_dev, int Hq, int Hkv,
-                            int D, float scale, int split_keys, int nsplit, float* part_o, float* part_ml,
-                            int kcap, const void* kd, const void* vd, hipStream_t stream) {
+// lkv_rows (pg_attention_rows; null for pg_attention): int32 [B] per-row key counts, see the entry point below.
+static int attention_impl(const void* q, long q_rs, void* o, long o_rs, const void* k, long k_bs, long k_hs,
+                          long k_rs, const void* vt, long vt_bs, long vt_hs, long vt_ds, const float* mask,
+                          long mask_bs, long mask_rs, int B, int Lq, int Lkv, const int* lkv_dev, int Hq, int Hkv,
+                          int D, float scale, int split_keys, int nsplit, float* part_o, float* part_ml,
+                          int kcap, const void* kd, const void* vd, const int* lkv_rows, hipStream_t stream) {
   PG_REQUIRE(B > 0 && Lq > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && D > 0 && D % 8 == 0 && D <= 256);
   // (split mode writes partials only: o is read by nobody, the merge is pg_attn_combine's or the o_proj prologue's)
   PG_REQUIRE(kcap >= 0 && kcap % 32 == 0 && q && (split_keys == 0 ? o != nullptr : (part_o && part_ml)));
@@ -1278,6 +1279,14 @@ extern "C" int pg_attention(const void* q, long q_rs, void* o, long o_rs, const 
              (const bf16_t*)vt, vt_bs, vt_hs, vt_ds, mask, mask_bs, mask_rs,
              Lq, Lkv, G, Hkv, D, lkv_dev, scale * 1.4426950408889634f, split_keys, part_o, part_ml,
              split_keys > 0 ? kcap : 0, 0, (const bf16_t*)kd, (const bf16_t*)vd};
+  if (lkv_rows) {
+    // one kv length per batch row.  Decode: Lkv + lkv_rows[b].  Prefill: lkv_rows[b] keys, clamped to [1, Lkv] in the
+    // kernels; the host's Lkv (the most any row holds) still picks the kernel form and its grid
+    a.lkv_dev = lkv_rows;
+    a.lkv_stride = 1;
+    a.lkv_max = split_keys > 0 ? 0x7fffffff : Lkv;
+    if (split_keys == 0) a.Lkv = 0;
+  }
   dim3 grid;
   // prefill with >= 1024 one-wave workgroups: the LDS-staged kernel (64 rows per workgroup share K/V);
   // needs 16-B aligned V^T rows / batch offsets
@@ -1364,6 +1373,36 @@ extern "C" int pg_attention(const void* q, long q_rs, void* o, long o_rs, const 
   return 0;
 }
 
+extern "C" int pg_attention(const void* q, long q_rs, void* o, long o_rs, const void* k, long k_bs, long k_hs,
+                            long k_rs, const void* vt, long vt_bs, long vt_hs, long vt_ds, const float* mask,
+                            long mask_bs, long mask_rs, int B, int Lq, int Lkv, const int* lkv_dev, int Hq, int Hkv,
+                            int D, float scale, int split_keys, int nsplit, float* part_o, float* part_ml,
+                            int kcap, const void* kd, const void* vd, hipStream_t stream) {
+  return attention_impl(q, q_rs, o, o_rs, k, k_bs, k_hs, k_rs, vt, vt_bs, vt_hs, vt_ds, mask, mask_bs, mask_rs, B, Lq,
+                        Lkv, lkv_dev, Hq, Hkv, D, scale, split_keys, nsplit, part_o, part_ml, kcap, kd, vd, nullptr,
+                        stream);
+}
+
+// pg_attention with one kv length per batch row, lkv_rows int32 [B] in device memory (prompts of different lengths in
+// one batch).  Prefill (split_keys == 0): row b's queries attend its first lkv_rows[b] keys, 1 <= lkv_rows[b] <= Lkv
+// (clamped); Lkv, the most any row holds, picks the kernel form exactly as for pg_attention, and every form takes the
+// per-row count: a row's workgroups walk only ceil(lkv_rows[b] / block) key blocks and mask the tail block at
+// lkv_rows[b]; with key splits (nsplit > 1) the row's blocks are dealt to the splits, splits left without a block write
+// the neutral partial (m = -inf, l = 0, O = 0) and the merge skips them.  Decode (split_keys > 0): row b attends
+// Lkv + lkv_rows[b] keys -- lkv_dev's role, one word per row.  K rows / V^T columns below Lkv (prefill) or kcap
+// (decode) must hold finite values: a masked key has weight exactly 0, but the flash and decode kernels do not zero
+// its V.  Every query row of the batch is computed (a padded row's queries attend the row's real keys).
+extern "C" int pg_attention_rows(const void* q, long q_rs, void* o, long o_rs, const void* k, long k_bs, long k_hs,
+                                 long k_rs, const void* vt, long vt_bs, long vt_hs, long vt_ds, const float* mask,
+                                 long mask_bs, long mask_rs, int B, int Lq, int Lkv, const int* lkv_rows, int Hq,
+                                 int Hkv, int D, float scale, int split_keys, int nsplit, float* part_o,
+                                 float* part_ml, int kcap, const void* kd, const void* vd, hipStream_t stream) {
+  PG_REQUIRE(lkv_rows != nullptr && B > 0 && Lkv >= (split_keys > 0 ? 0 : 1));
+  return attention_impl(q, q_rs, o, o_rs, k, k_bs, k_hs, k_rs, vt, vt_bs, vt_hs, vt_ds, mask, mask_bs, mask_rs, B, Lq,
+                        Lkv, nullptr, Hq, Hkv, D, scale, split_keys, nsplit, part_o, part_ml, kcap, kd, vd, lkv_rows,
+                        stream);
+}
+
 extern "C" int pg_attn_combine(const float* part_o, const float* part_ml, int B, int Hq, int Hkv, int D, int nsplit,
                                void* o, long o_rs, hipStream_t stream) {
   PG_REQUIRE(part_o && part_ml && o && B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 16 && nsplit >= 1 &&
@@ -1382,10 +1421,10 @@ extern "C" int pg_attn_combine(const float* part_o, const float* part_ml, int B,
 // splits per (batch, kv head) in granules of nw (2 or 4) blocks, nb rounds each (nw * nsplit <= kcap / 32 <=
 // nw * nsplit * nb); workspace part_o [B][Hkv][nsplit][16][D], part_ml [B][Hkv][nsplit][16][2] fp32; counters int32
 // [B * Hkv], zero before the first call (every call leaves them zero).  head_dim 32 or 256, D == head_dim.
-extern "C" int pg_attn_decode(const void* q, long q_rs, void* o, long o_rs, const void* kd, const void* vd, int B,
-                              int Lkv, const int* lkv_dev, int Hq, int Hkv, int D, float scale, int kcap, int nsplit,
-                              int nw, int nb, float* part_o, float* part_ml, int* counters, void* q8,
-                              float* q8_scale, long q8_ld, hipStream_t stream) {
+static int attn_decode_impl(const void* q, long q_rs, void* o, long o_rs, const void* kd, const void* vd, int B,
+                            int Lkv, const int* lkv_dev, int lkv_stride, int Hq, int Hkv, int D, float scale, int kcap,
+                            int nsplit, int nw, int nb, float* part_o, float* part_ml, int* counters, void* q8,
+                            float* q8_scale, long q8_ld, hipStream_t stream) {
   PG_REQUIRE(q && B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 16 && (D == 32 || D == 256));
   const bool pipe = (nw & PG_ATTN_PIPE) != 0 && nb >= 2;      // the double-buffered form (head_dim 256, 4 waves)
   nw &= ~PG_ATTN_PIPE;
@@ -1399,7 +1438,7 @@ extern "C" int pg_attn_decode(const void* q, long q_rs, void* o, long o_rs, cons
              ((uintptr_t)vd & 15) == 0 && ((uintptr_t)o & 15) == 0);
   AttnArgs a{(const bf16_t*)q, q_rs, (bf16_t*)o, o_rs, nullptr, 0, 0, 0, nullptr, 0, 0, 0, nullptr, 0, 0,
              1, Lkv, Hq / Hkv, Hkv, D, lkv_dev, scale * 1.4426950408889634f, 32 * 4 * nb, part_o, part_ml, kcap, 0,
-             (const bf16_t*)kd, (const bf16_t*)vd};
+             (const bf16_t*)kd, (const bf16_t*)vd, lkv_stride, 0x7fffffff};
   const dim3 grid(nsplit, Hkv, B);
 #define PG_DEC_LAUNCH(DP_, DT_, NW_, PIPE_)                                                                 \
   hipLaunchKernelGGL((attn_decode_fused_kernel<DP_, DT_, NW_, PIPE_>), grid, dim3(NW_ * 64), 0, stream, a, nb, \
@@ -1417,6 +1456,27 @@ extern "C" int pg_attn_decode(const void* q, long q_rs, void* o, long o_rs, cons
 #undef PG_DEC_LAUNCH
   PG_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int pg_attn_decode(const void* q, long q_rs, void* o, long o_rs, const void* kd, const void* vd, int B,
+                              int Lkv, const int* lkv_dev, int Hq, int Hkv, int D, float scale, int kcap, int nsplit,
+                              int nw, int nb, float* part_o, float* part_ml, int* counters, void* q8,
+                              float* q8_scale, long q8_ld, hipStream_t stream) {
+  return attn_decode_impl(q, q_rs, o, o_rs, kd, vd, B, Lkv, lkv_dev, 0, Hq, Hkv, D, scale, kcap, nsplit, nw, nb,
+                          part_o, part_ml, counters, q8, q8_scale, q8_ld, stream);
+}
+
+// pg_attn_decode with one kv length per batch row: row b attends Lkv + lkv_rows[b] keys (lkv_rows int32 [B], device
+// memory).  The same kernel instances, the same load order: the row's word is read where the shared word was.  Every
+// split of every row arrives at its (row, kv head) ticket whatever the row's length, so rows whose later splits hold
+// no key merge like the others (an empty split's partial is m = -inf, l = 0 and weighs 0).
+extern "C" int pg_attn_decode_rows(const void* q, long q_rs, void* o, long o_rs, const void* kd, const void* vd, int B,
+                                   int Lkv, const int* lkv_rows, int Hq, int Hkv, int D, float scale, int kcap,
+                                   int nsplit, int nw, int nb, float* part_o, float* part_ml, int* counters, void* q8,
+                                   float* q8_scale, long q8_ld, hipStream_t stream) {
+  PG_REQUIRE(lkv_rows != nullptr && B > 0);
+  return attn_decode_impl(q, q_rs, o, o_rs, kd, vd, B, Lkv, lkv_rows, 1, Hq, Hkv, D, scale, kcap, nsplit, nw, nb,
+                          part_o, part_ml, counters, q8, q8_scale, q8_ld, stream);
 }
 
 // The attention weights the reference's modules return, for callers of the module API that read them: probs = 1

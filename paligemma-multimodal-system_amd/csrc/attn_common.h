@@ -22,7 +22,7 @@ struct AttnArgs {
   const bf16_t* vt; long vt_bs, vt_hs, vt_ds;
   const float* mask; long mask_bs, mask_rs;
   int Lq, Lkv, G, Hkv, D;
-  const int* lkv_dev;      // if set: Lkv = *lkv_dev + Lkv
+  const int* lkv_dev;      // if set: Lkv = *lkv_dev + Lkv (lkv_dev[b] with lkv_stride 1)
   float scale_log2;        // softmax scale * log2(e)
   int split_keys;          // split mode if > 0 (keys per wave)
   float* part_o;           // [B][Hkv][nsplit][16][DT*16]
@@ -33,7 +33,21 @@ struct AttnArgs {
                            // [B][Hkv][pf_splits][Lq*G][DT*16] / [..][2], merged by attn_pf_combine_kernel)
   const bf16_t* kd;        // decode-order cache copies [B][Hkv][kcap][D] (dec_koff / dec_voff): the kcap > 0 decode
   const bf16_t* vd;        // kernels read K and V only from these
+  int lkv_stride;          // 0: lkv_dev is one word shared by the batch; 1: int32 [B], row b reads lkv_dev[b]
+                           // (pg_attention_rows / pg_attn_decode_rows: prompts of different lengths in one batch)
+  int lkv_max;             // prefill with lkv_stride 1: row b attends min(max(lkv_dev[b], 1), lkv_max) keys
 };
+
+// the kv-length word of batch row b (a zero word when there is none: no select on the loaded value)
+static __device__ __forceinline__ const int* attn_lkv_ptr(const AttnArgs& a, int b) {
+  return a.lkv_dev ? a.lkv_dev + b * a.lkv_stride : &pg_zero_word;
+}
+// keys batch row b attends in prefill mode (wave-uniform): Lkv (+ the shared device word), or row b's own count
+static __device__ __forceinline__ int attn_prefill_keys(const AttnArgs& a, int b) {
+  if (!a.lkv_dev) return a.Lkv;
+  const int n = __builtin_amdgcn_readfirstlane(a.lkv_dev[b * a.lkv_stride]) + a.Lkv;
+  return a.lkv_stride ? min(max(n, 1), a.lkv_max) : n;
+}
 
 // Decode-order copies of the static KV cache (ABI 6).  The QKV epilogue writes every appended k / v twice: to the
 // canonical K [.][Smax][D] / V^T [.][D][Smax] (prefill attention, the reference KVCache views) and to these copies,
@@ -138,7 +152,7 @@ __device__ __forceinline__ void attn_decode_split(const AttnArgs& a, int b, int 
   const int hq = kvh * a.G + rr % a.G;
   int lkv_raw = 0;
   if constexpr (FULL)
-    lkv_raw = __hip_atomic_load(a.lkv_dev ? a.lkv_dev : &pg_zero_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    lkv_raw = __hip_atomic_load(attn_lkv_ptr(a, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
   bf16x8 qf[KS];
   const bf16_t* qp = a.q + ((long)b * a.Lq + pos) * a.q_rs + (long)hq * D;
@@ -200,7 +214,7 @@ __device__ __forceinline__ void attn_decode_split(const AttnArgs& a, int b, int 
   u32x4 vr[DT];
   if (FULL) load_block(min(kbeg, a.kcap - 32), a.kcap, kfa, kfb, vr);
   else if (pre) load_block(kbeg, a.kcap, kfa, kfb, vr);
-  const int Lkv = (FULL ? __builtin_amdgcn_readfirstlane(lkv_raw) : (a.lkv_dev ? *a.lkv_dev : 0)) + a.Lkv;
+  const int Lkv = (FULL ? __builtin_amdgcn_readfirstlane(lkv_raw) : *attn_lkv_ptr(a, b)) + a.Lkv;
   const int kend = min(Lkv, kbeg + a.split_keys);
   // one 32-key block from the loaded registers: mask by the kv length, S^T, online softmax, P.V.  A block with
   // no valid key (a peeled first block past the kv length) leaves (o, m, l) = (0, -inf, 0) untouched.
@@ -322,8 +336,7 @@ __device__ __forceinline__ void attn_decode_block32(const AttnArgs& a, int b, in
   const int rr = c < R ? c : R - 1;              // rows past Lq*G read row R - 1 (never stored): no select
   const int pos = rr / a.G;
   const int hq = kvh * a.G + rr % a.G;
-  const int lkv_raw =
-      __hip_atomic_load(a.lkv_dev ? a.lkv_dev : &pg_zero_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int lkv_raw = __hip_atomic_load(attn_lkv_ptr(a, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   bf16x8 qf[KS];
   const bf16_t* qp = a.q + ((long)b * a.Lq + pos) * a.q_rs + (long)hq * DP;
 #pragma unroll

@@ -10,7 +10,9 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const float
   const bool m1 = (epi_flags & PG_TILE_M1) != 0;
   const bool n64 = (epi_flags & PG_TILE_N64) != 0;
   const int epi = epi_flags & 0xFF;
-  PG_REQUIRE((epi_flags & ~(0xFF | PG_W_FRAG | PG_FP8 | PG_TILE_M1 | PG_TILE_N64)) == 0 && epi <= PG_EPI_F32_RES);
+  const bool slot_rows = (epi_flags & PG_SLOT_ROWS) != 0;
+  PG_REQUIRE((epi_flags & ~(0xFF | PG_W_FRAG | PG_FP8 | PG_TILE_M1 | PG_TILE_N64 | PG_SLOT_ROWS)) == 0 &&
+             epi <= PG_EPI_F32_RES);
   if (m1) PG_REQUIRE(!fp8 && !n64 && M >= 256 && M <= 288 && (fa == nullptr || fa->pro_mode == 0));
   if (n64) PG_REQUIRE(M > 16);
   PG_REQUIRE(M > 0 && N > 0 && K > 0 && ksplit >= 1 && W != nullptr && C != nullptr);
@@ -23,6 +25,9 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const float
   if (fa) f = *fa;
   EpiArgs e{bias, C, ldc, M, N, aux, aux_rows, (bf16_t*)aux_out, aux_ld, aux_n, f};
   PG_REQUIRE(f.pro_mode >= 0 && f.pro_mode <= 5);
+  // per-row slot words: the q|k|v append (one word per batch row) or the attention-merge prologue (one per row)
+  if (slot_rows) PG_REQUIRE(fa && f.slot_dev && (epi == PG_EPI_QKV_ROPE || (f.pro_mode == 2 && f.akeys > 0)));
+  e.slot_rows = slot_rows ? 1 : 0;
   if (f.pro_mode == 5)
     PG_REQUIRE(fp8 && frag && epi == PG_EPI_F32 && M <= 32 && f.amax_in && f.amax_ld >= 1 && A != nullptr &&
                lda >= K && lda % 8 == 0 && ((uintptr_t)A & 15) == 0 && K % 128 == 0 && (K / 128) % ksplit == 0 &&

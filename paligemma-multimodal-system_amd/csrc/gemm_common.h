@@ -181,6 +181,7 @@ __device__ __forceinline__ f32x4 load4_guard(const float* __restrict__ p, int n0
 #define PG_TILE_M1 0x400  // one row tile of all M (256..288) rows (include/pghip.h)
 #define PG_TILE_N64 0x800 // 64 x 64 tiles (include/pghip.h)
 #define PG_FP8 0x200      // A and W fp8 e4m3 with row scales (PgFusedArgs a_scale / w_scale), M > 16
+#define PG_SLOT_ROWS 0x1000  // PgFusedArgs.slot_dev is int32 [B], one word per batch row (include/pghip.h)
 
 // fp8 GEMV: the wide form (x once per workgroup in LDS, waves split N), gemm_gemv8.hip; gemm.hip checks against it
 #ifndef PG_GEMV8_WIDE
@@ -201,7 +202,16 @@ struct EpiArgs {
   int aux_ld;
   int aux_n;
   PgFusedArgs f;
+  int slot_rows;             // PG_SLOT_ROWS: 1 = f.slot_dev holds one word per batch row (0: one shared word)
 };
+
+// The cache slot base of output row m's batch: slot_base (+ the device word -- the batch's one, or with PG_SLOT_ROWS
+// the word of row m's batch index m / rows_per_batch).
+__device__ __forceinline__ int epi_slot0(const EpiArgs& e, int m) {
+  const PgFusedArgs& f = e.f;
+  if (!f.slot_dev) return f.slot_base;
+  return f.slot_base + (e.slot_rows ? f.slot_dev[m / f.rows_per_batch] : *f.slot_dev);
+}
 
 // fp8 dequantisation of one accumulator fragment: C[m][n0..n0+3] *= a_scale[m] * w_scale[n0..n0+3]
 __device__ __forceinline__ void scale_acc(const EpiArgs& e, int m, int n0, f32x4& v) {
@@ -266,7 +276,8 @@ __device__ __forceinline__ void epi_qkv_rope4_core(const EpiArgs& e, int m, int 
   const int d0 = second ? half + ii : ii;             // original dim of element 0
   const int b = m / f.rows_per_batch, i = m % f.rows_per_batch;
   const int slot = slot0 + i;
-  const bool in_cache = slot < f.smax;                // a token past the static cache is not appended
+  // a token past the static cache is not appended (nor one in front of it: a per-row slot word below -slot_base)
+  const bool in_cache = (unsigned)slot < (unsigned)f.smax;
   const int Hq = f.q_heads, Hkv = f.kv_heads;
   const int KV = Hkv * D;
   if (blk < Hq + Hkv) {
@@ -316,7 +327,7 @@ __device__ __forceinline__ void epi_qkv_rope4_pr(const EpiArgs& e, int m, int n0
       sn[j] = sp[j];
     }
   }
-  epi_qkv_rope4_core(e, m, n0, v, pr, cs, sn, f.slot_base + (f.slot_dev ? *f.slot_dev : 0));
+  epi_qkv_rope4_core(e, m, n0, v, pr, cs, sn, epi_slot0(e, m));
 }
 
 __device__ __forceinline__ void epi_qkv_rope4(const EpiArgs& e, int m, int n0, f32x4 v) {

@@ -295,14 +295,15 @@ __device__ __forceinline__ void gemv_prologue(const EpiArgs& e, int M, int K, in
       return;
     }
     const int Seff = (f.slot_dev && f.akeys > 0) ? min(S, (*f.slot_dev + f.akeys) / f.akeys) : S;
-    for (int idx = t; idx < items; idx += 256) {
-      const int m = idx / (nh * D4), rem = idx % (nh * D4), hl = rem / D4, d4 = rem % D4;
+    // one (row, head, 4 dims) item merged over its first Sn splits
+    auto merge_item = [&](int idx, int m, int Sn) {
+      const int rem = idx % (nh * D4), hl = rem / D4, d4 = rem % D4;
       const int hq = h0 + hl;
       const long base0 = (((long)m * f.kv_heads + hq / G) * S) * 16 + (hq % G);
       float mx = -INFINITY, den = 0.f;
       f32x4 num = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 8
-      for (int sp = 0; sp < Seff; ++sp) {
+      for (int sp = 0; sp < Sn; ++sp) {
         const long bs = base0 + (long)sp * 16;
         const float ms = f.part_ml[bs * 2], ls = f.part_ml[bs * 2 + 1];
         const f32x4 o4 = *(const f32x4*)(f.part_o + bs * f.dtw + d4 * 4);
@@ -318,6 +319,16 @@ __device__ __forceinline__ void gemv_prologue(const EpiArgs& e, int M, int K, in
       pk[0] = pack_bf2(num[0] * inv, num[1] * inv);
       pk[1] = pack_bf2(num[2] * inv, num[3] * inv);
       *(u32x2*)(xs + m * ldx + hl * D + d4 * 4) = pk;
+    };
+    if (e.slot_rows) {
+      // PG_SLOT_ROWS: row m's own count, its kv length before this token being slot_dev[m] + slot_base (a branch on
+      // a kernel argument: the shared-length loop below keeps its wave-uniform trip count)
+      for (int idx = t; idx < items; idx += 256) {
+        const int m = idx / (nh * D4);
+        merge_item(idx, m, min(S, (f.slot_dev[m] + f.slot_base + f.akeys) / f.akeys));
+      }
+    } else {
+      for (int idx = t; idx < items; idx += 256) merge_item(idx, idx / (nh * D4), Seff);
     }
   }
   __syncthreads();
@@ -400,8 +411,10 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
     rope_p = e.f.pos[r < M ? r : M - 1];
     // a vector load (counted in order with the stream, unlike a scalar load whose wait lands early); a null
     // slot_dev reads a zero word instead of a select on the loaded value
-    rope_slot_raw = __hip_atomic_load(e.f.slot_dev ? e.f.slot_dev : &pg_zero_word, __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_AGENT);
+    // (PG_SLOT_ROWS: the word of this lane's row's batch; the same load, issued at the same place)
+    const int* slot_p = e.f.slot_dev ? e.f.slot_dev : &pg_zero_word;
+    if (e.slot_rows) slot_p += (r < M ? r : M - 1) / e.f.rows_per_batch;
+    rope_slot_raw = __hip_atomic_load(slot_p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 
   // element offset of a lane's 16-B piece s inside a CH-element chunk: PG_GEMV_CONTIG lays piece s of the 4

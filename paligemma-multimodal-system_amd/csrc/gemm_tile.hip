@@ -653,7 +653,7 @@ __global__ __launch_bounds__(256) void gemm_finalize_kernel(const float* __restr
     bool roped;
     const int ii = rope_freq_index(e.f, c0, &roped);
     const int p = e.f.pos[m];
-    const int slot0 = e.f.slot_base + (e.f.slot_dev ? *e.f.slot_dev : 0);
+    const int slot0 = epi_slot0(e, m);
     const f32x4 v = sum4(c0), pr = sum4(c0 ^ 8);
     f32x4 cs = {1.f, 1.f, 1.f, 1.f}, sn = {0.f, 0.f, 0.f, 0.f};
     if (roped) {
@@ -852,6 +852,11 @@ extern "C" int pg_gemm_finalize(const float* part, int nsplit, void* C, int ldc,
   PgFusedArgs f{};
   if (fa) f = *fa;
   EpiArgs e{nullptr, C, ldc, M, N, nullptr, 0, (bf16_t*)aux_out, aux_ld, aux_n, f};
+  if (epi & PG_SLOT_ROWS) {                       // per-row cache slots (PG_EPI_QKV_ROPE only)
+    epi &= ~PG_SLOT_ROWS;
+    PG_REQUIRE(epi == PG_EPI_QKV_ROPE && f.slot_dev);
+    e.slot_rows = 1;
+  }
   const int NO = epi == PG_EPI_BF16_GELU_MUL ? N / 2 : N;
   const long items = (long)M * (NO / 4);
   const dim3 grid((unsigned)((items + 255) / 256));

@@ -185,7 +185,13 @@ class PaliGemmaForConditionalGeneration(nn.Module):
     def generate(self, input_ids, pixel_values, attention_mask=None, max_new_tokens: int = 100,
                  do_sample: bool = False, temperature: float = 0.8, top_p: float = 0.9, uniforms=None,
                  stop_token: Optional[int] = 1):
-        """The token loop of inference.py:45-82 on the engine (vision once, hipGraph-replayed decode steps)."""
+        """The token loop of inference.py:45-82 on the engine (vision once, hipGraph-replayed decode steps).
+
+        Several prompts of different lengths go in one call as a right-padded batch (PaliGemmaProcessor.batch):
+        input_ids padded with pad_token_id, attention_mask ones over each row's own tokens and zeros after them.
+        Row b is then a request of its first mask[b].sum() tokens and generates what it generates alone at B = 1
+        (the reference attends its padding; forward() keeps that).  A mask that is not right-padded, or a row without
+        a real token, raises ValueError."""
         eng = self.engine(input_ids.device)
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)

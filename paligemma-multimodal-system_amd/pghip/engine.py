@@ -63,6 +63,25 @@ def rope_tables(dim: int, n_pos: int, base: float, device):
     return freqs.cos().to(device).contiguous(), freqs.sin().to(device).contiguous()
 
 
+def mask_lengths(attention_mask: torch.Tensor) -> torch.Tensor:
+    """Per-row token counts (int64 [B], on the host) of a right-padded attention mask [B][L]: real tokens first, then
+    zeros.  Raises ValueError -- on the host, before anything is launched -- for a row without a real token and for a
+    zero in front of a one (left padding, a hole): generate treats row b as a request of its first len_b tokens, which
+    only a right-padded mask describes."""
+    if attention_mask.dim() != 2:
+        raise ValueError(f"attention_mask must be [B][L], got {tuple(attention_mask.shape)}")
+    m = attention_mask.detach().to("cpu") != 0
+    lens = m.sum(-1)
+    if bool((lens == 0).any()):
+        raise ValueError(f"attention_mask: row {int((lens == 0).nonzero()[0])} holds no real token")
+    want = torch.arange(m.shape[1])[None, :] < lens[:, None]
+    if not torch.equal(m, want):
+        bad = int((m != want).any(-1).nonzero()[0])
+        raise ValueError(f"attention_mask: row {bad} is not right-padded (a zero in front of a one); pad on the right "
+                         "(utils.load_hf_model pins padding_side='right')")
+    return lens
+
+
 class KVStore:
     """Static KV cache: K [layers][B][Smax][nkv*hd] (roped), V^T [layers][B][nkv*hd][Smax], bf16, plus the
     decode-order copies kd / vd [layers][B][nkv][Smax][hd] that the QKV epilogue writes beside them and the decode
@@ -77,6 +96,7 @@ class KVStore:
         self.kd = torch.zeros(layers, B * Smax * kv_dim, dtype=torch.bfloat16, device=device)
         self.vd = torch.zeros(layers, B * Smax * kv_dim, dtype=torch.bfloat16, device=device)
         self.length = 0
+        self.ragged = False      # set by a prefill with per-row lengths: row b holds its own len_b < length keys
 
     def copy_prefix_from(self, old: "KVStore", n: int):
         """Grow: the first n positions of every layer of a smaller store (canonical and decode-order copies)."""
@@ -322,9 +342,14 @@ class PaliGemmaEngine:
 
     def gemma_prefill(self, x_resid: torch.Tensor, positions: torch.Tensor, cache: KVStore, B: int, L: int,
                       logits_rows: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
-                      want_hidden: bool = False, want_logits: bool = True, taps: Optional[list] = None):
+                      want_hidden: bool = False, want_logits: bool = True, taps: Optional[list] = None,
+                      kv_rows: Optional[torch.Tensor] = None):
         """GemmaForCausalLM.forward after the *sqrt(H) (modeling_gemma.py:510-534) on resid fp32 [B*L][H]
-        (already scaled).  Fills cache slots [0, L).  logits_rows: int32 rows to emit logits for (None = all)."""
+        (already scaled).  Fills cache slots [0, L).  logits_rows: int32 rows to emit logits for (None = all).
+        kv_rows (int32 [B] on the device; a right-padded batch): row b's queries attend its first kv_rows[b] keys
+        only (ops.attention_rows); the padding's own rows compute finite values nobody reads."""
+        if kv_rows is not None and mask is not None:
+            raise ValueError("gemma_prefill: per-row key counts replace the additive mask, pass one of them")
         w = self.w
         T = B * L
         H, I, nh, nkv, hd = w.hidden, w.inter, w.heads, w.kv_heads, w.head_dim
@@ -349,11 +374,15 @@ class PaliGemmaEngine:
                                 kc=cache.k[i], vtc=cache.vt[i], smax=cache.Smax, q_heads=nh, kv_heads=nkv,
                                 kd=cache.kd[i], vd=cache.vd[i])
             self._lin(xin, Lw, "qkv", qb, ops.EPI_QKV_ROPE, T, fa=fa)
-            ops.attention(qb, nh * hd, attn, attn.stride(0), cache.k[i], cache.Smax * kvd, hd, kvd,
-                          cache.vt[i], kvd * cache.Smax, hd * cache.Smax, cache.Smax,
-                          B=B, Lq=L, Lkv=L, Hq=nh, Hkv=nkv, D=hd, scale=1.0 / math.sqrt(hd),
-                          mask=mask, mask_bs=(mask.stride(0) if mask is not None else 0),
-                          mask_rs=(mask.stride(-2) if mask is not None else 0), **ks_t)
+            a_args = (qb, nh * hd, attn, attn.stride(0), cache.k[i], cache.Smax * kvd, hd, kvd,
+                      cache.vt[i], kvd * cache.Smax, hd * cache.Smax, cache.Smax)
+            if kv_rows is not None:
+                ops.attention_rows(*a_args, B=B, Lq=L, Lkv=L, lkv_rows=kv_rows, Hq=nh, Hkv=nkv, D=hd,
+                                   scale=1.0 / math.sqrt(hd), **ks_t)
+            else:
+                ops.attention(*a_args, B=B, Lq=L, Lkv=L, Hq=nh, Hkv=nkv, D=hd, scale=1.0 / math.sqrt(hd),
+                              mask=mask, mask_bs=(mask.stride(0) if mask is not None else 0),
+                              mask_rs=(mask.stride(-2) if mask is not None else 0), **ks_t)
             n_o = self._row_parallel(attn, Lw, "o", part, T, s_o, resid=x_resid)
             xin = self._norm(x_resid, Lw["post_w"], part, n_o, xn, T)
             if self._mx_prefill(T):
@@ -369,6 +398,7 @@ class PaliGemmaEngine:
             if taps is not None:
                 taps.append((x_resid + part[:ns].sum(0)).clone())
         cache.length = L
+        cache.ragged = kv_rows is not None
         rows = logits_rows.numel() if logits_rows is not None else T
         xf = self._buf("t_xf", (rows, H), torch.bfloat16)
         hid = torch.empty(rows, H, dtype=torch.float32, device=self.device) if want_hidden else None
@@ -613,6 +643,9 @@ class PaliGemmaEngine:
             "hist": torch.zeros(max_steps + 1, B, dtype=torch.int64, device=self.device),
             "ws": torch.empty(B * 64 * 2, dtype=torch.float32, device=self.device),
             "chain": self._chain_ok(sampler),
+            # per-row kv lengths (a prefill with a right-padded mask): pos[b] - 1 is row b's kv length before its
+            # token and the slot it appends at, so the step reads st["pos"] where it read st["kv_len"]
+            "ragged": bool(getattr(cache, "ragged", False)),
         }
         return st
 
@@ -653,6 +686,7 @@ class PaliGemmaEngine:
         ns_ws = max(nsplit, ops.decode_plan(B, nkv, cache.Smax)[0]) if B > self.FUSE_MAX_B else nsplit
         return SimpleNamespace(
             B=B, route=route, so=so, sd=sd, SK=SK, nsplit=nsplit, dt=dt, cos_t=cos_t, sin_t=sin_t,
+            ragged=False, sr=0,         # per-row kv lengths (decode_step sets them from the state)
             res_a=self._buf("d_res_a", (B, H), torch.float32),
             res_b=self._buf("d_res_b", (B, H), torch.float32),
             xn=self._buf("d_xn", (B, H), torch.bfloat16),
@@ -668,6 +702,8 @@ class PaliGemmaEngine:
         w = self.w
         B = st["ids"].numel()
         ws = self._decode_ws(B, cache)
+        ws.ragged = bool(st.get("ragged"))
+        ws.sr = ops.SLOT_ROWS if ws.ragged else 0   # OR-ed into the epi of the launches that read slot_dev
         chain = bool(st.get("chain")) and self._chain_ok(sampler)
         if not chain:                               # chained: the previous sample() wrote res_a already
             ops.embed_merge(st["ids"], None, w.embed, feats, feats.shape[0] if feats is not None else 0, ws.res_a,
@@ -724,26 +760,37 @@ class PaliGemmaEngine:
         device-resident kv length (canonical and decode-order copies)."""
         w = self.w
         return dict(head_dim=w.head_dim, cos_t=ws.cos_t, sin_t=ws.sin_t, pos=st["pos"], rows_per_batch=1,
-                    slot_dev=st["kv_len"], slot_base=0, kc=cache.k[i], vtc=cache.vt[i], smax=cache.Smax,
-                    q_heads=w.heads, kv_heads=w.kv_heads, kd=cache.kd[i], vd=cache.vd[i])
+                    kc=cache.k[i], vtc=cache.vt[i], smax=cache.Smax, q_heads=w.heads, kv_heads=w.kv_heads,
+                    kd=cache.kd[i], vd=cache.vd[i], **self._slot_kw(st, ws))
+
+    @staticmethod
+    def _slot_kw(st: dict, ws) -> dict:
+        """Where a decode launch finds a row's kv length before its token (= its append slot): the batch's one
+        kv_len word, or with per-row lengths pos[b] - 1 (slot = position - 1 for real tokens; launched with ws.sr)."""
+        if ws.ragged:
+            return dict(slot_dev=st["pos"], slot_base=-1)
+        return dict(slot_dev=st["kv_len"], slot_base=0)
 
     def _attn_split(self, i: int, st: dict, cache: KVStore, ws):
         """Layer i's split-KV decode attention: the (O, m, l) partials of ws.nsplit splits of ws.SK keys."""
         w = self.w
         nh, nkv, hd = w.heads, w.kv_heads, w.head_dim
         kvd = nkv * hd
-        ops.attention(ws.qb, nh * hd, None, nh * hd, cache.k[i], cache.Smax * kvd, hd, kvd,
-                      cache.vt[i], kvd * cache.Smax, hd * cache.Smax, cache.Smax,
-                      B=ws.B, Lq=1, Lkv=1, lkv_dev=st["kv_len"], Hq=nh, Hkv=nkv, D=hd,
-                      scale=1.0 / math.sqrt(hd), split_keys=ws.SK, nsplit=ws.nsplit, part_o=ws.part_o,
-                      part_ml=ws.part_ml, kcap=cache.Smax, kd=cache.kd[i], vd=cache.vd[i])
+        a_args = (ws.qb, nh * hd, None, nh * hd, cache.k[i], cache.Smax * kvd, hd, kvd,
+                  cache.vt[i], kvd * cache.Smax, hd * cache.Smax, cache.Smax)
+        kw = dict(B=ws.B, Lq=1, Hq=nh, Hkv=nkv, D=hd, scale=1.0 / math.sqrt(hd), split_keys=ws.SK, nsplit=ws.nsplit,
+                  part_o=ws.part_o, part_ml=ws.part_ml, kcap=cache.Smax, kd=cache.kd[i], vd=cache.vd[i])
+        if ws.ragged:                               # row b holds pos[b] keys once its token is appended
+            ops.attention_rows(*a_args, Lkv=0, lkv_rows=st["pos"], **kw)
+        else:
+            ops.attention(*a_args, Lkv=1, lkv_dev=st["kv_len"], **kw)
 
     def _combine_kw(self, st: dict, ws) -> dict:
         """PgFusedArgs fields of an o_proj GEMV that merges the split-KV partials in its prologue."""
         w = self.w
         return dict(pro_mode=ops.PRO_ATTN_COMBINE, part_o=ws.part_o, part_ml=ws.part_ml, asplit=ws.nsplit,
                     head_dim=w.head_dim, dtw=ws.dt, q_per_kv=w.heads // w.kv_heads, kv_heads=w.kv_heads,
-                    slot_dev=st["kv_len"], akeys=ws.SK)
+                    akeys=ws.SK, **self._slot_kw(st, ws))
 
     def _decode_attn_merged(self, i: int, st: dict, cache: KVStore, ws, want_fp8: bool = False):
         """Split-KV decode attention of layer i for B > FUSE_MAX_B rows, merged: one pg_attn_decode launch
@@ -765,7 +812,8 @@ class PaliGemmaEngine:
             if want_fp8 and self.ATTN_FP8_OUT and ops.attn_decode_q8_ok(nh, nkv, hd, plan[1]):
                 x8 = self._x8(B, nh * hd)
             ops.attn_decode(ws.qb, nh * hd, attn, nh * hd, cache.kd[i], cache.vd[i],
-                            B=B, Lkv=1, lkv_dev=st["kv_len"], Hq=nh, Hkv=nkv, D=hd, scale=1.0 / math.sqrt(hd),
+                            B=B, Lkv=0 if ws.ragged else 1, lkv_dev=st["pos"] if ws.ragged else st["kv_len"],
+                            rows=ws.ragged, Hq=nh, Hkv=nkv, D=hd, scale=1.0 / math.sqrt(hd),
                             kcap=cache.Smax, part_o=ws.part_o, part_ml=ws.part_ml,
                             counters=self._zeros("d_dec_cnt", (B * nkv,), torch.int32), plan=plan,
                             q8=x8[0] if x8 else None, q8_scale=x8[1] if x8 else None)
@@ -807,10 +855,10 @@ class PaliGemmaEngine:
         for i, Lw in enumerate(w.tl):
             fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res_a, resid_out=res_b, partials=part, nsplit=ns,
                                 norm_w=Lw["in_w"], eps=1e-6, **self._rope_kw(i, st, cache, ws))
-            ops.gemm_fused(None, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag, M=B)
+            ops.gemm_fused(None, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag | ws.sr, M=B)
             self._attn_split(i, st, cache, ws)
             fa = ops.fused_args(**self._combine_kw(st, ws))
-            ops.gemm_fused(None, Lw["o_w"], part, fa, epi=ops.EPI_F32 | w.wflag, M=B, ksplit=ws.so)
+            ops.gemm_fused(None, Lw["o_w"], part, fa, epi=ops.EPI_F32 | w.wflag | ws.sr, M=B, ksplit=ws.so)
             n_o = self._allreduce_slabs(part, ws.so)
             fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res_b, resid_out=res_a, partials=part, nsplit=n_o,
                                 norm_w=Lw["post_w"], eps=1e-6)
@@ -862,10 +910,10 @@ class PaliGemmaEngine:
                     # the step starts from a zero accumulator whatever an earlier (interrupted) step left in it: layer 0's
                     # q|k|v GEMV does not read it and clears it before layer 0's o_proj adds into it
                     fa.amax_zero, fa.amax_zero_n = fx.data_ptr(), fx.numel() * 2
-                ops.gemm_fused(None, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag, M=B)
+                ops.gemm_fused(None, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag | ws.sr, M=B)
             else:
                 fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=f.ss_d, ss_ld=tiles, ss_n=f.n_ss, eps=1e-6, **rope)
-                ops.gemm_fused(f.xq, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag, M=B)
+                ops.gemm_fused(f.xq, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag | ws.sr, M=B)
             if not merge_in_gemv:
                 attn = self._decode_attn_merged(i, st, cache, ws)
                 fa = ops.fused_args(norm_w=Lw["post_w"], **fin_o)
@@ -875,10 +923,11 @@ class PaliGemmaEngine:
                 if f.add_o:
                     fa = ops.fused_args(resid_in=res if (fx is not None and i == 0) else None, status=f.fx_st,
                                         **self._combine_kw(st, ws))
-                    ops.gemm_fused(None, Lw["o_w"], f.add_dst, fa, epi=f.add_epi | w.wflag, M=B, ksplit=ws.so)
+                    ops.gemm_fused(None, Lw["o_w"], f.add_dst, fa, epi=f.add_epi | w.wflag | ws.sr, M=B, ksplit=ws.so)
                 else:
                     fa = ops.fused_args(norm_w=Lw["post_w"], **fin_o, **self._combine_kw(st, ws))
-                    ops.gemm_fused(None, Lw["o_w"], part, fa, epi=ops.EPI_F32_FIN | w.wflag, M=B, ksplit=ws.so)
+                    ops.gemm_fused(None, Lw["o_w"], part, fa, epi=ops.EPI_F32_FIN | w.wflag | ws.sr, M=B,
+                                   ksplit=ws.so)
             self._mlp_fin(i, ws, f)
         return f.xq, f.ss_d, tiles, f.n_ss
 
@@ -940,11 +989,11 @@ class PaliGemmaEngine:
             fa = ops.fused_args(**self._rope_kw(i, st, cache, ws))
             if mxn:                                 # MX rows of x*(1+w); the q|k|v GEMV applies rstd
                 ops.norm_residual_mx(res, Lw["in_w"], x8n, xsn, ssn, partials=part, nsplit=ns)
-                ops.gemm8(x8n, None, Lw["qkv_w8f"], Lw["qkv_s8"], ws.qb, epi=ops.EPI_QKV_ROPE, M=B, fa=fa, frag=True,
-                          mx_in=xsn, ss_in=ssn)
+                ops.gemm8(x8n, None, Lw["qkv_w8f"], Lw["qkv_s8"], ws.qb, epi=ops.EPI_QKV_ROPE | ws.sr, M=B, fa=fa,
+                          frag=True, mx_in=xsn, ss_in=ssn)
             else:
                 xin = self._norm(res, Lw["in_w"], part, ns, ws.xn, B)
-                self._lin(xin, Lw, "qkv", ws.qb, ops.EPI_QKV_ROPE, B, fa=fa)
+                self._lin(xin, Lw, "qkv", ws.qb, ops.EPI_QKV_ROPE | ws.sr, B, fa=fa)
             attn = self._decode_attn_merged(i, st, cache, ws, want_fp8=self._fp8_rows(B))
             self._lin(attn, Lw, "o", part, ops.EPI_F32, B, ksplit=ws.so)
             n_o = self._allreduce_slabs(part, ws.so)
@@ -973,8 +1022,8 @@ class PaliGemmaEngine:
         """Next ids from logits [B][V] (greedy or top-p); advance=True also moves pos / kv_len on.  A chained
         state (decode_state) also gets the next step's input rows: pass the request's image features."""
         kw = dict(hist=st["hist"], step=st["step"])
-        if advance:
-            kw.update(pos=st["pos"], kv_len=st["kv_len"])
+        if advance:     # (per-row lengths: pos[b] is the row's length too, and the samplers leave a null kv_len alone)
+            kw.update(pos=st["pos"], kv_len=None if st.get("ragged") else st["kv_len"])
         if st.get("chain") and self._chain_ok(sampler):
             w = self.w
             B = st["ids"].numel()
@@ -989,8 +1038,17 @@ class PaliGemmaEngine:
     # ------------------------------------------------------------------ full request
     def prefill_request(self, input_ids: torch.Tensor, pixel_values: torch.Tensor, attention_mask: torch.Tensor,
                         max_new_tokens: int, feats: Optional[torch.Tensor] = None):
-        """Vision + merge + Gemma prefill; returns (cache, feats, last-position logits [B][V], next positions)."""
+        """Vision + merge + Gemma prefill; returns (cache, feats, last-position logits [B][V], next positions).
+        The mask must be right-padded (mask_lengths); row b is then a request of its first len_b tokens: its keys stop
+        at len_b (per-row prefill attention), its logits come from position len_b - 1, and the returned cache is marked
+        ragged when any len_b < L, so decode_state / decode_step append and attend per row.  An all-ones mask takes the
+        same launches as before."""
         B, L = input_ids.shape
+        lens_h = mask_lengths(attention_mask)                   # host check, before any launch
+        ragged = bool((lens_h < L).any())
+        if ragged and self.tp > 1:
+            raise NotImplementedError("prompts of different lengths in one batch (a padded attention_mask) are not "
+                                      "supported under tensor parallelism (tp > 1); pad-free batches are")
         if feats is None:
             feats = self.vision(pixel_values)
         cache = self.new_cache(B, L + max_new_tokens + 1)
@@ -998,8 +1056,9 @@ class PaliGemmaEngine:
         self.embed_merge(input_ids.to(self.device), feats, resid)
         am = attention_mask.to(self.device)
         pos = am.cumsum(-1).masked_fill(am == 0, 1)                       # modeling_paligemma.py:195
-        rows = (torch.arange(B, device=self.device, dtype=torch.int32) * L + (L - 1)).contiguous()
-        logits, _ = self.gemma_prefill(resid, pos, cache, B, L, logits_rows=rows)
+        lens = lens_h.to(device=self.device, dtype=torch.int32).contiguous() if ragged else None
+        rows = torch.arange(B, device=self.device, dtype=torch.int32) * L + (lens - 1 if ragged else L - 1)
+        logits, _ = self.gemma_prefill(resid, pos, cache, B, L, logits_rows=rows.contiguous(), kv_rows=lens)
         nxt = am.sum(-1).to(torch.int32) + 1                              # modeling_paligemma.py:189
         return cache, feats, logits, nxt
 
@@ -1012,7 +1071,8 @@ class PaliGemmaEngine:
         SURVEY §8(f2)): every row decodes in the same static-shape graph until ALL rows have produced
         `stop_token` (checked every `check_every` steps, default 8, one host sync each) or max_new_tokens;
         a row's tokens after its EOS are replaced by `pad_token` in the [B][n] result, or dropped when
-        return_list=True (a list of per-row id lists, each ending at its EOS)."""
+        return_list=True (a list of per-row id lists, each ending at its EOS).  Rows of different prompt lengths:
+        a right-padded attention_mask (prefill_request); each row then generates what it generates alone at B = 1."""
         B = input_ids.shape[0]
         if check_every is None:
             check_every = 1 if B == 1 else 8

@@ -22,6 +22,7 @@ NORM_LAYER, NORM_RMS = 0, 1
 W_FRAG = 0x100   # OR into epi: W is fragment-packed (weights.frag_pack, include/pghip.h PG_W_FRAG)
 TILE_M1 = 0x400  # OR into epi: all 256..288 rows in one row tile (batch-1 prefill, include/pghip.h PG_TILE_M1)
 TILE_N64 = 0x800  # OR into epi: 64 x 64 output tiles (small-M prefill GEMMs, include/pghip.h PG_TILE_N64)
+SLOT_ROWS = 0x1000  # OR into epi: PgFusedArgs.slot_dev is int32 [B], one word per batch row (PG_SLOT_ROWS)
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -145,7 +146,7 @@ def gemm8(A8: torch.Tensor, a_scale: Optional[torch.Tensor], W8: torch.Tensor, w
         if mx_in is None or ss_in.stride(-1) != 1 or K % 1024 or not 0 < K // 1024 <= 4 or ss_in.shape[-1] < K // 1024:
             raise ValueError("pghip.gemm8: ss_in needs mx_in and fp32 [M][K/1024] sums of squares (K <= 4096)")
         fa.ss_in, fa.ss_ld, fa.ss_n, fa.eps = ss_in.data_ptr(), ss_in.stride(-2), K // 1024, float(eps)
-    e = epi & 0xFF
+    e = epi & (0xFF | SLOT_ROWS)
     ldc = out.stride(-2) if out.dim() >= 2 else out.shape[-1]
     if frag:
         if M > 32:
@@ -153,7 +154,7 @@ def gemm8(A8: torch.Tensor, a_scale: Optional[torch.Tensor], W8: torch.Tensor, w
         _lib.call("pg_gemm_fused", _p(A8), A8.stride(0), _p(W8), W8.stride(0), _p(bias), _p(out), ldc, M, N, K,
                   e | EPI_FP8 | W_FRAG, ksplit, _lib.C.byref(fa), _s())
         return out
-    s = finalize_split(M, N, K // 2) if ksplit == 1 and e in _FIN_EPIS and mx_out is None else 1
+    s = finalize_split(M, N, K // 2) if ksplit == 1 and (e & 0xFF) in _FIN_EPIS and mx_out is None else 1
     if s > 1:   # small M: fp32 slabs, then the epilogue (scales already applied inside the slabs)
         part = torch.empty(s, M, N, dtype=torch.float32, device=out.device)
         _lib.call("pg_gemm_fused", _p(A8), A8.stride(0), _p(W8), W8.stride(0), _p(bias), _p(part), N, M, N, K,
@@ -212,8 +213,8 @@ def gemm_fused(A: Optional[torch.Tensor], W: torch.Tensor, out: torch.Tensor, fa
     if s > 1:   # small-M prefill: split K into fp32 slabs, then the (RoPE / KV-append) epilogue
         part = torch.empty(s, M, N, dtype=torch.float32, device=out.device)
         _lib.call("pg_gemm", _p(A), lda, _p(W), W.stride(0), _p(bias), _p(part), N, M, N, K,
-                  (epi & ~0xFF) | EPI_F32, s, None, 0, None, 0, 0, _s())
-        _lib.call("pg_gemm_finalize", _p(part), s, _p(out), ldc, M, N, epi & 0xFF, None, 0, 0,
+                  (epi & ~(0xFF | SLOT_ROWS)) | EPI_F32, s, None, 0, None, 0, 0, _s())
+        _lib.call("pg_gemm_finalize", _p(part), s, _p(out), ldc, M, N, epi & (0xFF | SLOT_ROWS), None, 0, 0,
                   _lib.C.byref(fa), _s())
         return out
     _lib.call("pg_gemm_fused", _p(A), lda, _p(W), W.stride(0), _p(bias), _p(out), ldc, M, N, K, epi, ksplit,
@@ -278,6 +279,24 @@ def attention(q, q_rs, o, o_rs, k, k_bs, k_hs, k_rs, vt, vt_bs, vt_hs, vt_ds, *,
     decode kernels then read K and V from the decode-order copies kd / vd (decode_cache_pack)."""
     _lib.call("pg_attention", _p(q), q_rs, _p(o), o_rs, _p(k), k_bs, k_hs, k_rs, _p(vt), vt_bs, vt_hs, vt_ds,
               _p(mask), mask_bs, mask_rs, B, Lq, Lkv, _p(lkv_dev), Hq, Hkv, D, float(scale), split_keys, nsplit,
+              _p(part_o), _p(part_ml), int(kcap), _p(kd), _p(vd), _s())
+
+
+def _chk_rows(t, B: int, name: str):
+    _chk(t, torch.int32, name)
+    if not t.is_contiguous() or t.numel() < B:
+        raise ValueError(f"pghip: {name} must be a contiguous int32 tensor of B = {B} per-row kv lengths")
+
+
+def attention_rows(q, q_rs, o, o_rs, k, k_bs, k_hs, k_rs, vt, vt_bs, vt_hs, vt_ds, *, B, Lq, Lkv, lkv_rows, Hq, Hkv,
+                   D, scale, mask=None, mask_bs=0, mask_rs=0, split_keys=0, nsplit=0, part_o=None, part_ml=None,
+                   kcap=0, kd=None, vd=None):
+    """attention() with one kv length per batch row (pg_attention_rows): lkv_rows int32 [B] on the device.  Prefill:
+    row b attends its first lkv_rows[b] <= Lkv keys (Lkv picks the kernel form); decode (split_keys > 0): row b
+    attends Lkv + lkv_rows[b] keys."""
+    _chk_rows(lkv_rows, B, "lkv_rows")
+    _lib.call("pg_attention_rows", _p(q), q_rs, _p(o), o_rs, _p(k), k_bs, k_hs, k_rs, _p(vt), vt_bs, vt_hs, vt_ds,
+              _p(mask), mask_bs, mask_rs, B, Lq, Lkv, _p(lkv_rows), Hq, Hkv, D, float(scale), split_keys, nsplit,
               _p(part_o), _p(part_ml), int(kcap), _p(kd), _p(vd), _s())
 
 
@@ -362,11 +381,14 @@ _ATTN_PIPE_FLAG = 0x100
 
 
 def attn_decode(q, q_rs, o, o_rs, kd, vd, *, B, Lkv, lkv_dev, Hq, Hkv, D, scale, kcap, part_o, part_ml, counters,
-                plan=None, q8=None, q8_scale=None):
+                plan=None, q8=None, q8_scale=None, rows=False):
     """Batched decode attention with the split merge in the same launch (pg_attn_decode): o[b][hq*D + d] bf16 from
     q (one position per row) over the decode-order cache copies kd / vd; part_o / part_ml / counters are workspaces
     (counters int32 [B*Hkv], zeroed once).  q8 uint8 [B][>= Hq*D] / q8_scale f32 [B] (optional, one kv head and a
-    4-wave plan, see attn_decode_q8_ok): also the rows as fp8 e4m3, byte-identical to quant_fp8(o)."""
+    4-wave plan, see attn_decode_q8_ok): also the rows as fp8 e4m3, byte-identical to quant_fp8(o).
+    rows: lkv_dev is int32 [B], one kv length per batch row (pg_attn_decode_rows)."""
+    if rows:
+        _chk_rows(lkv_dev, B, "lkv_dev")
     nsplit, nw, nb = plan or decode_plan(B, Hkv, kcap)
     if q8 is not None:
         _chk(q8, torch.uint8, "q8")
@@ -377,9 +399,9 @@ def attn_decode(q, q_rs, o, o_rs, kd, vd, *, B, Lkv, lkv_dev, Hq, Hkv, D, scale,
         raise ValueError("pghip.attn_decode: partial workspace too small")
     if counters.dtype != torch.int32 or counters.numel() < B * Hkv:
         raise ValueError("pghip.attn_decode: counters must be int32 [B*Hkv]")
-    _lib.call("pg_attn_decode", _p(q), q_rs, _p(o), o_rs, _p(kd), _p(vd), B, Lkv, _p(lkv_dev), Hq, Hkv, D,
-              float(scale), kcap, nsplit, nw | (_ATTN_PIPE_FLAG if ATTN_PIPE else 0), nb, _p(part_o), _p(part_ml), _p(counters), _p(q8), _p(q8_scale),
-              q8.stride(0) if q8 is not None else 0, _s())
+    _lib.call("pg_attn_decode_rows" if rows else "pg_attn_decode", _p(q), q_rs, _p(o), o_rs, _p(kd), _p(vd), B, Lkv,
+              _p(lkv_dev), Hq, Hkv, D, float(scale), kcap, nsplit, nw | (_ATTN_PIPE_FLAG if ATTN_PIPE else 0), nb,
+              _p(part_o), _p(part_ml), _p(counters), _p(q8), _p(q8_scale), q8.stride(0) if q8 is not None else 0, _s())
 
 
 def attn_decode_q8_ok(Hq: int, Hkv: int, D: int, nw: int) -> bool:

@@ -83,3 +83,26 @@ class PaliGemmaProcessor:
                                 bos_token=self.tokenizer.bos_token)
         toks = self.tokenizer(s, return_tensors="pt", truncation=truncation, padding=padding)
         return {"pixel_values": pixel_values, **toks}
+
+    def batch(self, images: List, texts: List[str]) -> dict:
+        """Several (image, prompt) pairs as one right-padded batch for ``generate`` (the reference handles one pair,
+        its ``__call__`` asserts so): each pair goes through ``__call__`` alone -- so every row's ids are exactly its
+        single-request ids, quirks included -- and the rows are padded on the right with the tokenizer's pad id to
+        the longest.  Returns stacked ``pixel_values`` [B][3][S][S], ``input_ids`` [B][L] and ``attention_mask``
+        [B][L] (ones over a row's own tokens, zeros over its padding); ``generate`` then gives every row what it
+        gives that pair alone."""
+        if len(images) != len(texts) or not len(images):
+            raise ValueError(f"batch: {len(images)} images for {len(texts)} prompts (need one prompt per image)")
+        pad = self.tokenizer.pad_token_id
+        if pad is None:
+            raise ValueError("batch: the tokenizer has no pad token to pad the shorter prompts with")
+        rows = [self([im], [tx]) for im, tx in zip(images, texts)]
+        L = max(r["input_ids"].shape[1] for r in rows)
+        ids = torch.full((len(rows), L), pad, dtype=rows[0]["input_ids"].dtype)
+        mask = torch.zeros(len(rows), L, dtype=rows[0]["attention_mask"].dtype)
+        for b, r in enumerate(rows):
+            n = r["input_ids"].shape[1]
+            ids[b, :n] = r["input_ids"][0]
+            mask[b, :n] = r["attention_mask"][0]
+        return {"pixel_values": torch.cat([r["pixel_values"] for r in rows]), "input_ids": ids,
+                "attention_mask": mask}
