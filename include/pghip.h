@@ -173,6 +173,29 @@ typedef struct PgFusedArgs {
  * slot_dev = the rows' rotary positions and slot_base = -1 both are the row's kv length before this token. */
 #define PG_SLOT_ROWS 0x1000
 
+/* PG_W_FRAG13 (pg_gemm_fused, bf16, M <= 4; pghip/weights.py frag13_pack): W is the fragment-packed matrix with the
+ * exponent field of every bf16 stored as a 5-bit code relative to its block -- 13 bits per weight, lossless; the
+ * kernel rebuilds exactly the PG_W_FRAG operands and runs them in the same order, so results are bit-identical.
+ * Block (t, b) = rows 16t..16t+15 x the two 64-k chunks c = 8i + w and c + 4 (i = b / 4, w = b % 4) that one GEMV
+ * wave consumes back to back; it holds, for lane L = 16g + r, the 32 weights W[16t + r][64(c + 4h) + 16g + 8s + 2p + o]
+ * (h, s, o < 2, p < 4).  Per weight: one byte sign << 7 | mantissa7 and one code: 0 = exponent field 0 (zero,
+ * denormals), c >= 1 = exponent field base + c - 1, base = the block's smallest non-zero exponent field (1 for a block
+ * without one).  A matrix packs when every block's largest field - base <= 30.
+ * Block (t, b) starts at byte (t * K/128 + b) * 3328:
+ *   [   0, 1024)  lane L's 16 bytes at 16L: byte 4p + 2o + s = the sign/mantissa byte of (h = 0, s, p, o)
+ *   [1024, 2048)  the same for h = 1
+ *   [2048, 3072)  lane L's code words q0..q3 (little-endian dwords) at 2048 + 16L
+ *   [3072, 3328)  lane L's code word q4 at 3072 + 4L
+ * Pair P = 4(2h + s) + p, P < 15, has its o = 0 code in bits [5k, 5k + 5) and its o = 1 code in bits [16 + 5k, 21 + 5k)
+ * of q[P / 3], k = P % 3; pair 15's two codes are spread over the spare bits: bit d of the o = 0 code is bit 15 of
+ * q[d], bit d of the o = 1 code is bit 31 of q[d] (d < 5).
+ * After the N/16 * K/128 blocks comes one little-endian uint16 per block, in block order: base | zflag << 8, zflag = 1
+ * when the block holds a code 0.  `W` points at the first block; ldw must equal K.
+ * Requires N % 16 == 0, K % 128 == 0, (K / 64) % (8 * ksplit) == 0, W 16-byte aligned, and one of the batch-1 decode
+ * forms: PG_EPI_QKV_ROPE or PG_EPI_BF16_GELU_MUL with pro_mode 1, PG_EPI_FX_ADD with pro_mode 0 or 2, PG_EPI_F32_FIN
+ * with pro_mode 0, PG_EPI_F32 with pro_mode 4; anything else returns hipErrorInvalidValue. */
+#define PG_W_FRAG13 0x2000
+
 /* C = A[M][K] . W[N][K]^T with fused epilogue.  nn.Linear call sites: siglip.py:59-62,71-75,156,177-178,
  * 183-185; paligemma.py:57,64; gemma.py:205-207,212-218,255-259,274-278,356,484,523.  K % 32 == 0
  * (% 64 when M > 16), N % 4 == 0.  M <= 16 takes the weight-streaming GEMV path. */

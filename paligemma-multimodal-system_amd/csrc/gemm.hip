@@ -11,8 +11,19 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const float
   const bool n64 = (epi_flags & PG_TILE_N64) != 0;
   const int epi = epi_flags & 0xFF;
   const bool slot_rows = (epi_flags & PG_SLOT_ROWS) != 0;
-  PG_REQUIRE((epi_flags & ~(0xFF | PG_W_FRAG | PG_FP8 | PG_TILE_M1 | PG_TILE_N64 | PG_SLOT_ROWS)) == 0 &&
+  const bool frag13 = (epi_flags & PG_W_FRAG13) != 0;
+  PG_REQUIRE((epi_flags & ~(0xFF | PG_W_FRAG | PG_FP8 | PG_TILE_M1 | PG_TILE_N64 | PG_SLOT_ROWS | PG_W_FRAG13)) == 0 &&
              epi <= PG_EPI_F32_RES);
+  // the 13-bit pack: the batch-1 decode forms only, whole 128-k blocks per wave in every split
+  if (frag13) {
+    const int pm = fa ? fa->pro_mode : 0;
+    PG_REQUIRE(!frag && !fp8 && !m1 && !n64 && W != nullptr && ((uintptr_t)W & 15) == 0 && M >= 1 && M <= 4 &&
+               N > 0 && N % 16 == 0 && K > 0 && K % 128 == 0 && ldw == K && ksplit >= 1 && ksplit <= 64 &&
+               (K / 64) % (8 * ksplit) == 0);
+    PG_REQUIRE((epi == PG_EPI_QKV_ROPE && pm == 1) || (epi == PG_EPI_BF16_GELU_MUL && pm == 1) ||
+               (epi == PG_EPI_FX_ADD && (pm == 0 || pm == 2)) || (epi == PG_EPI_F32_FIN && pm == 0) ||
+               (epi == PG_EPI_F32 && pm == 4));
+  }
   if (m1) PG_REQUIRE(!fp8 && !n64 && M >= 256 && M <= 288 && (fa == nullptr || fa->pro_mode == 0));
   if (n64) PG_REQUIRE(M > 16);
   PG_REQUIRE(M > 0 && N > 0 && K > 0 && ksplit >= 1 && W != nullptr && C != nullptr);
@@ -35,7 +46,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const float
   if (f.amax_out) PG_REQUIRE(fp8 && frag && epi == PG_EPI_BF16_GELU_MUL && M <= 32 && f.amax_ld >= 1 &&
                              ((K >> 7) + ksplit - 1) / ksplit * 128 <= 4096 && PG_GEMV8_WIDE);
   // (ABI 12: also the bf16 fragment-packed GEMV, which clears the batch-1 decode's fixed-point accumulator with it)
-  if (f.amax_zero) PG_REQUIRE(frag && f.amax_zero_n >= 0 &&
+  if (f.amax_zero) PG_REQUIRE((frag || frag13) && f.amax_zero_n >= 0 &&
                               (fp8 ? f.amax_zero_n <= 4096
                                    : (M <= 16 && f.amax_zero_n <= 16384 && f.amax_zero_n % 4 == 0 &&
                                       ((uintptr_t)f.amax_zero & 15) == 0)));
@@ -111,7 +122,8 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const float
   }
   // M <= 16 -> the weight-streaming GEMV, else the tile GEMM; PG_W_FRAG only for the Gemma epilogues (the
   // launchers run the row-major form of the others)
-  const int rc = M <= 16 ? pg_dispatch_gemv(epi, frag, a, lda, w, ldw, K, ksplit, e, stream)
+  const int rc = frag13  ? pg_dispatch_gemv13(epi, a, lda, W, K, ksplit, e, stream)
+                 : M <= 16 ? pg_dispatch_gemv(epi, frag, a, lda, w, ldw, K, ksplit, e, stream)
                          : pg_dispatch_tile(epi, frag, false, a, lda, w, ldw, K, ksplit, e, stream, m1, n64);
   if (rc) return rc;
   PG_LAUNCH_CHECK();

@@ -338,7 +338,51 @@ __device__ __forceinline__ void gemv_prologue(const EpiArgs& e, int M, int K, in
 // straight-line code with unconditional loads, so hipcc's s_waitcnt bookkeeping stays exact: each chunk's MFMAs
 // wait only for that chunk (vmcnt(N), N = younger loads), instead of the conservative vmcnt(0) that the runtime
 // loop and its exec-masked loads produce at every ring turn (the ring drained before its first MFMA).
-template <int EPI, int NT, int U, int DEPTH, int PRO, bool FRAG, int CPW = 0>
+// PG_W_FRAG13 (FRAG == 2; include/pghip.h): one lane's share of a 16-row x 128-k block, 13 dwords for 32 weights -- the
+// sign/mantissa bytes of the block's two 64-k chunks, the 5-bit exponent codes, and the block's base | zflag << 8 word
+struct W13 {
+  u32x4 sm[2];
+  u32x4 cq;
+  unsigned c4;
+  unsigned bz;
+};
+// The block's four MFMA operands op[h][s], bit for bit the u32x4 pieces the PG_W_FRAG layout holds for chunk h, piece
+// s.  Z: the block holds a code 0 (exponent field 0: no base added to that weight); wave-uniform, from the base table.
+template <bool Z>
+__device__ __forceinline__ void decode13(const W13& b, unsigned bm, u32x4 (&op)[2][2]) {
+  unsigned q[5] = {b.cq[0], b.cq[1], b.cq[2], b.cq[3], b.c4};
+  // (opaque copies: the compiler otherwise hoists the 20 shifts both decodes share above their branch and keeps them
+  // live across it -- 12 to 20 more VGPRs per kernel, one wave per SIMD fewer on q|k|v and the finalised down)
+#pragma unroll
+  for (int d = 0; d < 5; ++d) asm volatile("" : "+v"(q[d]));
+  const unsigned badd = bm * 0x00800080u;              // (base - 1) << 7 in both halves (scalar)
+#pragma unroll
+  for (int P = 0; P < 16; ++P) {
+    // the pair's two codes at bits 7..11 and 23..27, the exponent field's place in a bf16 pair
+    unsigned e;
+    if (P < 15) {
+      const unsigned w = q[P / 3];
+      e = (P % 3 == 0 ? w << 7 : P % 3 == 1 ? w << 2 : w >> 3) & 0x0f800f80u;
+    } else {
+      e = ((q[0] >> 8) & 0x00800080u) | ((q[1] >> 7) & 0x01000100u) | ((q[2] >> 6) & 0x02000200u) |
+          ((q[3] >> 5) & 0x04000400u) | ((q[4] >> 4) & 0x08000800u);
+    }
+    if constexpr (Z) {
+      const unsigned nz = ((e + 0x0f800f80u) >> 5) & 0x00800080u;   // 1 << 7 per half whose code is not 0
+      e += __umul24(nz, bm);
+    } else {
+      e += badd;
+    }
+    const int h = P >> 3, s = (P >> 2) & 1, p = P & 3;
+    // sm dword p = bytes (s 0, o 0), (s 1, o 0), (s 0, o 1), (s 1, o 1): each byte doubled into its half-word puts the
+    // sign at bit 15 and the mantissa at bits 0..6 (one v_perm), the rest is masked off as the exponent goes in
+    const unsigned x = b.sm[h][p];
+    const unsigned d = __builtin_amdgcn_perm(x, x, s == 0 ? 0x02020000u : 0x03030101u);
+    op[h][s][p] = (d & 0x807f807fu) | e;
+  }
+}
+
+template <int EPI, int NT, int U, int DEPTH, int PRO, int FRAG, int CPW = 0>
 __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W,
                                           int ldw, int K, const EpiArgs& e, const GemvIdx gi) {
   constexpr int CH = U * 32;
@@ -357,6 +401,9 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
   const int c0 = z * per_z;
   const int nch = min(nch_all - c0, per_z);
   const int mine = CPW > 0 ? CPW : (nch > wave ? (nch - wave + 3) / 4 : 0);   // chunks wave, wave+4, ...
+  // FRAG13: whole blocks (chunk pairs j = 2i, 2i + 1) per wave, the same count for every wave (host-checked)
+  constexpr int DB = DEPTH / 2;                 // ... blocks in flight
+  const int nb = CPW > 0 ? CPW / 2 : nch >> 3;
 
   const bf16_t* wrow[NT];
   const bf16_t* wfrag[NT];
@@ -422,8 +469,54 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
   // contiguous elements.  x uses the same map, so the k order inside the MFMA is consistent either way.
   constexpr int S_STRIDE = PG_GEMV_CONTIG ? 32 : 8;
   const int LANE_OFF = PG_GEMV_CONTIG ? g * 8 : g * 8 * U;
-  u32x4 wb[DEPTH][NT][U];
+  u32x4 wb[FRAG == 2 ? 1 : DEPTH][NT][U];
   u32x4 xb[DEPTH][U];
+  W13 wc[FRAG == 2 ? DB : 1][NT];
+  // block i of this wave: tile t's block (c0 / 8 + i) * 4 + wave, four lane-linear loads and the block's table word
+  auto loadw13 = [&](int i, W13 (&wv)[NT]) {
+    const int nblk = K >> 7;
+    const int bk = ((c0 >> 3) + i) * 4 + wave;
+    const char* w13 = (const char*)W;
+    const unsigned short* tab = (const unsigned short*)(w13 + (size_t)(e.N >> 4) * nblk * PG_F13_BLOCK);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const size_t blk = (size_t)min(tile0 + t, (e.N >> 4) - 1) * nblk + bk;
+      const char* p = w13 + blk * PG_F13_BLOCK;
+      constexpr bool hot = ((PG_GEMV_HOT & 1) && EPI == PG_EPI_QKV_ROPE) || ((PG_GEMV_HOT & 2) && PRO == 2);
+      if constexpr (PG_GEMV_FRAG_NT && !hot) {
+        wv[t].sm[0] = __builtin_nontemporal_load((const u32x4*)p + lane);
+        wv[t].sm[1] = __builtin_nontemporal_load((const u32x4*)(p + 1024) + lane);
+        wv[t].cq = __builtin_nontemporal_load((const u32x4*)(p + 2048) + lane);
+        wv[t].c4 = __builtin_nontemporal_load((const unsigned*)(p + 3072) + lane);
+      } else {
+        wv[t].sm[0] = ((const u32x4*)p)[lane];
+        wv[t].sm[1] = ((const u32x4*)(p + 1024))[lane];
+        wv[t].cq = ((const u32x4*)(p + 2048))[lane];
+        wv[t].c4 = ((const unsigned*)(p + 3072))[lane];
+      }
+      wv[t].bz = tab[blk];
+    }
+  };
+  // block i's 2 x U x NT MFMAs in the PG_W_FRAG order (chunk, piece, tile); the decode is register-only on both sides
+  // of its wave-uniform branch
+  auto mfma13 = [&](const W13 (&wv)[NT], const u32x4 (&x0)[U], const u32x4 (&x1)[U]) {
+    static_assert(FRAG != 2 || U == 2, "FRAG13 blocks are two 64-k chunks");
+    // (tile by tile: the tiles' accumulators are independent, each sees its own MFMAs in the PG_W_FRAG order)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      u32x4 op[2][2];
+      const unsigned bz = __builtin_amdgcn_readfirstlane(wv[t].bz);
+      const unsigned bm = (bz & 0xffu) - 1u;
+      if (bz & 0x100u) decode13<true>(wv[t], bm, op);
+      else decode13<false>(wv[t], bm, op);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+          acc[t] = mfma16(__builtin_bit_cast(bf16x8, op[h][s]), __builtin_bit_cast(bf16x8, h == 0 ? x0[s] : x1[s]),
+                          acc[t]);
+    }
+  };
   auto loadw = [&](int j, u32x4 (&wv)[NT][U]) {
     if constexpr (FRAG) {
       // fragment-packed weights: tile t's chunk c is U wave-instructions of 1 KiB, lane-linear; read once,
@@ -481,8 +574,15 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
   constexpr bool prew = STAGED && PG_GEMV_PREW;
   if (prew) {
 #pragma unroll
-    for (int d = 0; d < DEPTH; ++d)
-      if (CPW > 0 ? d < CPW : d < mine) loadw(d, wb[d]);
+    for (int d = 0; d < DEPTH; ++d) {
+      if constexpr (FRAG == 2) {
+        // (sched_barrier: the blocks' loads stay in ring order, so block 0's MFMAs wait for block 0 alone)
+        if (d < DB && (CPW > 0 ? d < CPW / 2 : d < nb)) loadw13(d, wc[d]);
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
+        if (CPW > 0 ? d < CPW : d < mine) loadw(d, wb[d]);
+      }
+    }
   }
   if constexpr (STAGED) {
     float* scratch = (float*)(dyn_smem + (((size_t)M * (Kr + XPAD) * 2 + 15) & ~(size_t)15));
@@ -492,11 +592,19 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
       gemv_prologue<PRO>(e, M, K, c0 * CH, nch * CH, xs, scratch, A, lda, gi);
   }
 #pragma unroll
-  for (int d = 0; d < DEPTH; ++d)
-    if (CPW > 0 ? d < CPW : d < mine) {
+  for (int d = 0; d < DEPTH; ++d) {
+    if constexpr (FRAG == 2) {
+      if (d < DB && (CPW > 0 ? d < CPW / 2 : d < nb)) {
+        if (!prew) loadw13(d, wc[d]);
+        loadx(2 * d, xb[2 * d]);
+        loadx(2 * d + 1, xb[2 * d + 1]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    } else if (CPW > 0 ? d < CPW : d < mine) {
       if (!prew) loadw(d, wb[d]);
       loadx(d, xb[d]);
     }
+  }
   // PG_EPI_F32_FIN: the residual rows and norm weights the tile's last-arriving split finalises are loaded now
   // (nothing else writes them in this launch), so the reducer's only round trip is the slab read
   f32x4 fin_r[NT], fin_w[NT];
@@ -528,7 +636,35 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
       rope_sn[t] = *(const f32x4*)(e.f.sin_t + off);
     }
   }
-  if constexpr (CPW > 0) {
+  if constexpr (FRAG == 2 && CPW > 0) {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < CPW / 2; ++i) {
+      const int d = i % DB;
+      mfma13(wc[d], xb[2 * d], xb[2 * d + 1]);
+      if (i + DB < CPW / 2) {
+        loadw13(i + DB, wc[d]);
+        loadx(2 * (i + DB), xb[2 * d]);
+        loadx(2 * (i + DB) + 1, xb[2 * d + 1]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  } else if constexpr (FRAG == 2) {
+    for (int base = 0; base < nb; base += DB) {
+#pragma unroll
+      for (int d = 0; d < DB; ++d) {
+        const int i = base + d;
+        if (i < nb) {
+          mfma13(wc[d], xb[2 * d], xb[2 * d + 1]);
+          if (i + DB < nb) {
+            loadw13(i + DB, wc[d]);
+            loadx(2 * (i + DB), xb[2 * d]);
+            loadx(2 * (i + DB) + 1, xb[2 * d + 1]);
+          }
+        }
+      }
+    }
+  } else if constexpr (CPW > 0) {
     // sched_barrier: the scheduler may not sink the ring's loads below later MFMAs (it otherwise trades the
     // chunks in flight for registers: vmcnt(8) = two chunks in flight on the down projection)
     __builtin_amdgcn_sched_barrier(0);
@@ -784,8 +920,12 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
   }
 }
 
-template <int EPI, int NT, int U, int DEPTH, int PRO, bool FRAG, int CPW = 0>
-__global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ A, int lda,
+// (the 13-bit gate/up GEMV is held to 4 waves per SIMD, its PG_W_FRAG twin's occupancy: left alone the allocator takes
+// 122 VGPRs + 12 AGPRs, three waves; told, it fits 128 without a spill)
+template <int EPI, int NT, int U, int DEPTH, int PRO, int FRAG, int CPW = 0>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(FRAG == 2 && CPW > 0 && EPI == PG_EPI_BF16_GELU_MUL ? 4 : 1, 8)))
+void gemv_kernel(const bf16_t* __restrict__ A, int lda,
                                                    const bf16_t* __restrict__ W, int ldw, int K, EpiArgs e) {
   gemv_body<EPI, NT, U, DEPTH, PRO, FRAG, CPW>(A, lda, W, ldw, K, e,
                                                GemvIdx{(int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y});
@@ -868,6 +1008,43 @@ static void launch_gemv(const bf16_t* A, int lda, const bf16_t* W, int ldw, int 
     case 4: launch_gemv_pro<EPI, 4, FRAG>(A, lda, W, ldw, K, ksplit, e, st); break;
     default: launch_gemv_pro<EPI, 0, FRAG>(A, lda, W, ldw, K, ksplit, e, st); break;
   }
+}
+
+// PG_W_FRAG13: the batch-1 decode forms, each with the depth and tile count of its PG_W_FRAG twin (launch_gemv_pro at
+// M <= 4) -- here the two-tile lm_head form takes every N.  CPW 4 and 8 are the chunk counts the decode shapes hit.
+template <int EPI, int NT, int DEPTH, int PRO>
+static void launch_gemv13(const bf16_t* A, int lda, const void* W, int K, int ksplit, const EpiArgs& e, hipStream_t st) {
+  static_assert(DEPTH % 2 == 0, "whole blocks in flight");
+  const int ntiles = e.N / 16;
+  const int per_z = K / 64 / ksplit;
+  size_t lds = 0;
+  if (PRO != 0 && PRO != 4) {
+    lds = (size_t)e.M * (per_z * 64 + XPAD) * 2;
+    lds = (lds + 15) & ~(size_t)15;
+    if (PRO == 1) lds += 64 * sizeof(float);
+  }
+  const dim3 grid((ntiles + NT - 1) / NT, ksplit);
+  const bf16_t* w = (const bf16_t*)W;
+  switch (PG_GEMV_CPW ? per_z / 4 : 0) {
+    case 4: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, 2, 4>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
+    case 8: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, 2, 8>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
+    default: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, 2, 0>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
+  }
+}
+
+int pg_dispatch_gemv13(int epi, const bf16_t* A, int lda, const void* W, int K, int ksplit, const EpiArgs& e,
+                       hipStream_t st) {
+  const int pm = e.f.pro_mode;
+  if (e.M > 4 || (K / 64) % (8 * ksplit)) return (int)hipErrorInvalidValue;
+  if (epi == PG_EPI_QKV_ROPE && pm == 1) launch_gemv13<PG_EPI_QKV_ROPE, 1, PG_GEMV_D1, 1>(A, lda, W, K, ksplit, e, st);
+  else if (epi == PG_EPI_FX_ADD && pm == 2) launch_gemv13<PG_EPI_FX_ADD, 1, PG_GEMV_D1, 2>(A, lda, W, K, ksplit, e, st);
+  else if (epi == PG_EPI_FX_ADD && pm == 0) launch_gemv13<PG_EPI_FX_ADD, 1, PG_GEMV_D1, 0>(A, lda, W, K, ksplit, e, st);
+  else if (epi == PG_EPI_F32_FIN && pm == 0) launch_gemv13<PG_EPI_F32_FIN, 1, PG_GEMV_D1, 0>(A, lda, W, K, ksplit, e, st);
+  else if (epi == PG_EPI_BF16_GELU_MUL && pm == 1)
+    launch_gemv13<PG_EPI_BF16_GELU_MUL, 2, PG_GEMV_D2, 1>(A, lda, W, K, ksplit, e, st);
+  else if (epi == PG_EPI_F32 && pm == 4) launch_gemv13<PG_EPI_F32, 2, PG_GEMV_LM_D, 4>(A, lda, W, K, ksplit, e, st);
+  else return (int)hipErrorInvalidValue;
+  return 0;
 }
 
 int pg_dispatch_gemv(int epi, bool frag, const bf16_t* A, int lda, const bf16_t* W, int ldw, int K, int ksplit,

@@ -187,6 +187,13 @@ class PaliGemmaEngine:
     # fp8 linears of 17..32 rows (batched decode, the lm_head of a 17..32-row batch) on the weight-streaming fp8 GEMV
     # (fragment-packed e4m3 weights, csrc/gemm.hip gemv8_kernel) instead of the LDS-staged fp8 tile GEMM
     FP8_GEMV = os.environ.get("PG_FP8_GEMV", "1") != "0"
+    # B <= FUSE_MAX_B single rank, bf16: the decode GEMVs stream the lossless 13-bit weight pack (weights.frag13_pack,
+    # PG_W_FRAG13) where a matrix has one -- same bits out, 18.75 % fewer weight bytes in.  W13_FORMS: the
+    # launches that take it (a form that does not beat its PG_W_FRAG twin in the kernel profile leaves this list)
+    W13 = os.environ.get("PG_W13", "1") != "0"
+    # (measured, profiles/w13_kernel_stats_{parent,new}.csv: gate/up 22.4 -> 19.4 us, down 12.3 -> 10.8, the finalised
+    # down 13.4 -> 12.8, lm_head 150.6 -> 127.4; q|k|v 4.8 -> 5.5 and o_proj 5.1 -> 5.3 lost and stay PG_W_FRAG)
+    W13_FORMS = ("gu", "down", "lm")
 
     def __init__(self, cfg: dict, weights: PackedWeights, device="cuda", comm=None):
         self.cfg = cfg
@@ -713,7 +720,8 @@ class PaliGemmaEngine:
             # final RMSNorm folded into the lm_head GEMV: x' = resid*(1+w) from the last down_proj, rstd on the outputs
             logits = self._buf("d_logits", (B, w.vocab_local_pad), torch.float32)
             fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=ss, ss_ld=tiles, ss_n=n_ss, eps=1e-6)
-            ops.gemm_fused(xq, w.lm_w, logits, fa, epi=ops.EPI_F32 | w.wflag, M=B, bias=w.lm_bias)
+            lm_w, wf, nk = self._dec_w({"lm_w": w.lm_w, "lm_w13": w.lm_w13}, "lm", B, fx=self.DECODE_ADD == "fx")
+            ops.gemm_fused(xq, lm_w, logits, fa, epi=ops.EPI_F32 | wf, M=B, bias=w.lm_bias, **nk)
             logits = logits[:, :w.vocab]
         else:
             layers = self._decode_layers_fused if ws.route == "fused" else self._decode_layers_unfused
@@ -867,6 +875,17 @@ class PaliGemmaEngine:
             ns = self._allreduce_slabs(part, ws.sd)
         return ns
 
+    def _dec_w(self, d, name: str, B: int, ksplit: int = 1, fx: bool = True):
+        """(W, layout flag, N / K keywords) of the decode launch of d[name + "_w"] at B rows on the fin route: the 13-bit
+        pack when the switch is on, the matrix has one, the launch is a batch-1 form of the fixed-point route (fx) and
+        every wave of a split owns whole 128-k blocks; else the bf16 fragment pack, as before."""
+        W = d[name + "_w"]
+        p13 = d.get(name + "_w13")
+        if (self.W13 and fx and p13 is not None and name in self.W13_FORMS and B <= self.FUSE_MAX_B and self.tp == 1
+                and (W.shape[1] // 64) % (8 * ksplit) == 0):
+            return p13, ops.W_FRAG13, dict(N=W.shape[0], K=W.shape[1])
+        return W, self.w.wflag, {}
+
     def _decode_layers_fin(self, st: dict, cache: KVStore, ws):
         """Decode layers (single rank, B <= FUSE_MAX_B) in 5 launches with in-kernel split-K finalisation:
         o_proj and down_proj add their split-K slabs into the residual in place (the last-arriving split of
@@ -910,7 +929,8 @@ class PaliGemmaEngine:
                     # the step starts from a zero accumulator whatever an earlier (interrupted) step left in it: layer 0's
                     # q|k|v GEMV does not read it and clears it before layer 0's o_proj adds into it
                     fa.amax_zero, fa.amax_zero_n = fx.data_ptr(), fx.numel() * 2
-                ops.gemm_fused(None, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag | ws.sr, M=B)
+                qkv_w, wf, nk = self._dec_w(Lw, "qkv", B, fx=fx is not None)
+                ops.gemm_fused(None, qkv_w, ws.qb, fa, epi=ops.EPI_QKV_ROPE | wf | ws.sr, M=B, **nk)
             else:
                 fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=f.ss_d, ss_ld=tiles, ss_n=f.n_ss, eps=1e-6, **rope)
                 ops.gemm_fused(f.xq, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag | ws.sr, M=B)
@@ -923,7 +943,8 @@ class PaliGemmaEngine:
                 if f.add_o:
                     fa = ops.fused_args(resid_in=res if (fx is not None and i == 0) else None, status=f.fx_st,
                                         **self._combine_kw(st, ws))
-                    ops.gemm_fused(None, Lw["o_w"], f.add_dst, fa, epi=f.add_epi | w.wflag | ws.sr, M=B, ksplit=ws.so)
+                    o_w, wf, nk = self._dec_w(Lw, "o", B, ws.so, fx=fx is not None)
+                    ops.gemm_fused(None, o_w, f.add_dst, fa, epi=f.add_epi | wf | ws.sr, M=B, ksplit=ws.so, **nk)
                 else:
                     fa = ops.fused_args(norm_w=Lw["post_w"], **fin_o, **self._combine_kw(st, ws))
                     ops.gemm_fused(None, Lw["o_w"], part, fa, epi=ops.EPI_F32_FIN | w.wflag | ws.sr, M=B,
@@ -944,17 +965,19 @@ class PaliGemmaEngine:
         if f.add_o:
             fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res if fx is None else None, fx=fx, nsplit=0,
                                 norm_w=Lw["post_w"], eps=1e-6)
-            ops.gemm_fused(None, Lw["gu_w"], ws.h, fa, epi=ops.EPI_BF16_GELU_MUL | w.wflag, M=B)
+            gu_w, wf, nk = self._dec_w(Lw, "gu", B, fx=fx is not None)
+            ops.gemm_fused(None, gu_w, ws.h, fa, epi=ops.EPI_BF16_GELU_MUL | wf, M=B, **nk)
         else:
             fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=f.ss_o, ss_ld=f.tiles, ss_n=f.n_ss, eps=1e-6)
             ops.gemm_fused(f.xq, Lw["gu_w"], ws.h, fa, epi=ops.EPI_BF16_GELU_MUL | w.wflag, M=B)
+        down_w, wf, nk = self._dec_w(Lw, "down", B, ws.sd, fx=fx is not None)
         if f.add_down and not last:
-            ops.gemm_fused(ws.h, Lw["down_w"], f.add_dst, ops.fused_args(status=f.fx_st), epi=f.add_epi | w.wflag,
-                           M=B, ksplit=ws.sd)
+            ops.gemm_fused(ws.h, down_w, f.add_dst, ops.fused_args(status=f.fx_st), epi=f.add_epi | wf, M=B,
+                           ksplit=ws.sd, **nk)
             return
         nxt_w = w.final_w if last else w.tl[i + 1]["in_w"]
         fa = ops.fused_args(fin_cnt=f.cnt, fin_resid=res, ss_out=f.ss_d, ss_ld=f.tiles, fin_x=f.xq, norm_w=nxt_w, fx=fx)
-        ops.gemm_fused(ws.h, Lw["down_w"], ws.part, fa, epi=ops.EPI_F32_FIN | w.wflag, M=B, ksplit=ws.sd)
+        ops.gemm_fused(ws.h, down_w, ws.part, fa, epi=ops.EPI_F32_FIN | wf, M=B, ksplit=ws.sd, **nk)
 
     def _split_keys(self, B: int, Smax: int) -> int:
         """Keys per decode-attention split: 32 (one MFMA block) at small batch; at B > FUSE_MAX_B (separate

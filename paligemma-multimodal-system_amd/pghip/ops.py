@@ -23,6 +23,7 @@ W_FRAG = 0x100   # OR into epi: W is fragment-packed (weights.frag_pack, include
 TILE_M1 = 0x400  # OR into epi: all 256..288 rows in one row tile (batch-1 prefill, include/pghip.h PG_TILE_M1)
 TILE_N64 = 0x800  # OR into epi: 64 x 64 output tiles (small-M prefill GEMMs, include/pghip.h PG_TILE_N64)
 SLOT_ROWS = 0x1000  # OR into epi: PgFusedArgs.slot_dev is int32 [B], one word per batch row (PG_SLOT_ROWS)
+W_FRAG13 = 0x2000  # OR into epi (gemm_fused, M <= 4): W is the lossless 13-bit pack (weights.frag13_pack, PG_W_FRAG13)
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -196,17 +197,27 @@ def fused_args(**kw) -> "_lib.PgFusedArgs":
 
 def gemm_fused(A: Optional[torch.Tensor], W: torch.Tensor, out: torch.Tensor, fa, *, epi: int = EPI_BF16,
                M: int, bias: Optional[torch.Tensor] = None, ksplit: int = 1, N: Optional[int] = None,
-               ldc: Optional[int] = None, keep=None) -> torch.Tensor:
+               ldc: Optional[int] = None, keep=None, K: Optional[int] = None) -> torch.Tensor:
     """pg_gemm_fused: the GEMM with a fused prologue (x produced in-kernel) and/or RoPE/KV epilogue.
-    `fa` is a PgFusedArgs (see fused_args); `keep` holds tensors it points to alive for the call."""
-    _chk(W, torch.bfloat16, "W")
-    _chk_frag(W, epi)
+    `fa` is a PgFusedArgs (see fused_args); `keep` holds tensors it points to alive for the call.
+    With W_FRAG13 in epi, W is the flat uint8 pack of weights.frag13_pack and N, K name the matrix it holds."""
     if (epi & 0xFF) == EPI_FX_ADD:
         _chk(out, torch.int64, "out (the fixed-point accumulator)")
-    N = W.shape[0] if N is None else N
-    K = W.shape[1]
     if ldc is None:
         ldc = out.stride(-2) if out.dim() >= 2 else out.shape[-1]
+    if epi & W_FRAG13:
+        _chk(W, torch.uint8, "W (13-bit pack)")
+        if N is None or K is None or N % 16 or K % 128 or W.dim() != 1 or not W.is_contiguous() or \
+                W.numel() != (N // 16) * (K // 128) * 3330:
+            raise ValueError(f"pghip: a 13-bit packed W must be the flat pack of the [N][K] matrix named, got "
+                             f"{tuple(W.shape)} for N={N} K={K}")
+        _lib.call("pg_gemm_fused", _p(A), A.stride(0) if A is not None else K, _p(W), K, _p(bias), _p(out), ldc, M, N,
+                  K, epi, ksplit, _lib.C.byref(fa), _s())
+        return out
+    _chk(W, torch.bfloat16, "W")
+    _chk_frag(W, epi)
+    N = W.shape[0] if N is None else N
+    K = W.shape[1]
     lda = A.stride(0) if A is not None else K
     s = finalize_split(M, N, K) if (fa.pro_mode == 0 and A is not None and ksplit == 1 and
                                     (epi & 0xFF) in _FIN_EPIS) else 1

@@ -30,7 +30,11 @@ completes; the embedding gather, RMSNorm weights and the vision tower stay repli
 """
 from __future__ import annotations
 
+import logging
+
 import torch
+
+_log = logging.getLogger("pghip")
 
 
 def _rup(x: int, m: int) -> int:
@@ -70,6 +74,95 @@ def frag_unpack8(p: torch.Tensor) -> torch.Tensor:
     return p.reshape(N // 16, K // 128, 2, 4, 16, 16).permute(0, 4, 1, 2, 3, 5).contiguous().view(N, K)
 
 
+F13_BLOCK = 3328     # bytes of one 16-row x 128-k block of the 13-bit pack: 64 lanes x (32 B sign/mantissa + 20 B codes)
+_F13_TILES = 2048    # 16-row tiles packed per pass (bounds the temporaries of the lm_head's 16k tiles)
+
+
+def frag13_size(N: int, K: int) -> int:
+    """Bytes of the 13-bit pack of an [N][K] matrix: the blocks, then one uint16 (base | zflag << 8) per block."""
+    return (N // 16) * (K // 128) * (F13_BLOCK + 2)
+
+
+def _f13_blocks(w: torch.Tensor) -> torch.Tensor:
+    """bf16 bits of row-major W[16T][K] as int32 [T][ci][w][h][g][r][s][p][o]: block (t, b = 4 ci + w) holds chunks
+    c = 8 ci + w + 4h, lane 16g + r, element k = 64c + 16g + 8s + 2p + o (include/pghip.h PG_W_FRAG13)."""
+    N, K = w.shape
+    bits = w.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    #                     t        r   ci      h  w  g  s  p  o
+    bits = bits.view(N // 16, 16, K // 512, 2, 4, 4, 2, 4, 2)
+    return bits.permute(0, 2, 4, 3, 5, 1, 6, 7, 8)
+
+
+def frag13_pack(w: torch.Tensor):
+    """Row-major bf16 W[N][K] (N % 16 == 0, K % 512 == 0: whole groups of eight 64-k chunks) -> the lossless 13-bit
+    pack of include/pghip.h PG_W_FRAG13 as a flat uint8 tensor of frag13_size(N, K) bytes, or None when a block's
+    exponent fields span more than 31 codes (or the shape has no whole blocks): the caller keeps the PG_W_FRAG form."""
+    if w.dtype != torch.bfloat16 or w.dim() != 2:
+        raise TypeError("frag13_pack needs a 2-D bf16 matrix")
+    N, K = w.shape
+    if N % 16 or K % 512 or N == 0 or K == 0:
+        return None
+    nb = K // 128
+    blocks, tabs = [], []
+    for t0 in range(0, N // 16, _F13_TILES):
+        b = _f13_blocks(w[16 * t0:16 * (t0 + _F13_TILES)])
+        T = b.shape[0]
+        b = b.reshape(T, nb // 4, 4, 2, 4, 16, 2, 4, 2)
+        E = (b >> 7) & 0xFF
+        sm = ((b >> 8) & 0x80) | (b & 0x7F)
+        Ef = E.reshape(T, nb, -1)
+        base = torch.where(Ef > 0, Ef, torch.full_like(Ef, 256)).amin(-1)
+        base = torch.where(base == 256, torch.ones_like(base), base)          # no non-zero field: every code is 0
+        if bool(((Ef.amax(-1) - base) > 30).any()):
+            return None
+        zflag = (Ef == 0).any(-1).to(torch.int32)
+        c = torch.where(E > 0, E - base.view(T, nb // 4, 4, 1, 1, 1, 1, 1, 1) + 1, torch.zeros_like(E))
+        # sign/mantissa bytes: [T][ci][w] [h][g][r] [p][o][s] -> region h, lane 16g + r, byte 4p + 2o + s
+        smb = sm.permute(0, 1, 2, 3, 4, 5, 7, 8, 6).reshape(T, nb, 2 * 1024).to(torch.uint8)
+        # codes: [T][ci][w] [g][r] [P = 4(2h + s) + p] [o]
+        cp = c.permute(0, 1, 2, 4, 5, 3, 6, 7, 8).reshape(T, nb, 64, 16, 2).to(torch.int64)
+        ev, od = cp[..., 0], cp[..., 1]
+        q = torch.zeros(T, nb, 64, 5, dtype=torch.int64, device=w.device)
+        for P in range(15):
+            q[..., P // 3] |= (ev[..., P] << (5 * (P % 3))) | (od[..., P] << (16 + 5 * (P % 3)))
+        for d in range(5):
+            q[..., d] |= (((ev[..., 15] >> d) & 1) << 15) | (((od[..., 15] >> d) & 1) << 31)
+        qb = torch.stack([(q >> (8 * i)) & 0xFF for i in range(4)], -1).to(torch.uint8)    # [T][nb][64][5][4 bytes]
+        blocks.append(torch.cat([smb, qb[:, :, :, :4].reshape(T, nb, 1024), qb[:, :, :, 4].reshape(T, nb, 256)],
+                                -1).reshape(-1))
+        tb = base.to(torch.int32) | (zflag << 8)
+        tabs.append(torch.stack([tb & 0xFF, tb >> 8], -1).to(torch.uint8).reshape(-1))
+        del b, E, sm, Ef, c, smb, cp, ev, od, q, qb
+    return torch.cat(blocks + tabs)
+
+
+def frag13_unpack(p: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """Inverse of frag13_pack: the row-major bf16 [N][K] matrix, bit for bit."""
+    if p.dtype != torch.uint8 or p.numel() != frag13_size(N, K) or N % 16 or K % 512:
+        raise ValueError("frag13_unpack: not the 13-bit pack of an [N][K] matrix")
+    T, nb = N // 16, K // 128
+    blk = p[:T * nb * F13_BLOCK].view(T, nb, F13_BLOCK).to(torch.int64)
+    tab = p[T * nb * F13_BLOCK:].view(T, nb, 2).to(torch.int64)
+    base = tab[..., 0].view(T, nb, 1, 1, 1)
+    sm = blk[..., :2048].reshape(T, nb, 2, 64, 4, 2, 2)                     # [h][lane][p][o][s]
+    qb = torch.cat([blk[..., 2048:3072].reshape(T, nb, 64, 4, 4), blk[..., 3072:].reshape(T, nb, 64, 1, 4)], 3)
+    q = sum(qb[..., i] << (8 * i) for i in range(4))                         # [T][nb][64][5]
+    c = torch.zeros(T, nb, 64, 16, 2, dtype=torch.int64, device=p.device)
+    for P in range(15):
+        c[..., P, 0] = (q[..., P // 3] >> (5 * (P % 3))) & 31
+        c[..., P, 1] = (q[..., P // 3] >> (16 + 5 * (P % 3))) & 31
+    for d in range(5):
+        c[..., 15, 0] |= ((q[..., d] >> 15) & 1) << d
+        c[..., 15, 1] |= ((q[..., d] >> 31) & 1) << d
+    E = torch.where(c > 0, c + base - 1, torch.zeros_like(c))               # [T][nb][lane][P][o]
+    E = E.view(T, nb, 64, 2, 2, 4, 2).permute(0, 1, 3, 2, 5, 6, 4)           # -> [h][lane][p][o][s]
+    bits = ((sm & 0x80) << 8) | (E << 7) | (sm & 0x7F)                       # [T][nb = ci, w][h][g, r][p][o][s]
+    bits = bits.reshape(T, nb // 4, 4, 2, 4, 16, 4, 2, 2)
+    #        t  r  ci h  w  g  s  p  o
+    bits = bits.permute(0, 5, 1, 3, 2, 4, 8, 6, 7).reshape(N, K)
+    return torch.where(bits >= 32768, bits - 65536, bits).to(torch.int16).view(torch.bfloat16)
+
+
 def rope_row_perm(D: int) -> torch.Tensor:
     """Row order inside one D-wide head block for the fused RoPE epilogue: 16-row tile t holds
     dims 8t..8t+7 then D/2+8t..D/2+8t+7, so each lane's rotate_half partner is lane ^ 32."""
@@ -92,11 +185,16 @@ def quant_rows_fp8(w: torch.Tensor):
 
 class PackedWeights:
     def __init__(self, cfg: dict, get, device="cuda", parts=("vision", "proj", "text"), tp_rank: int = 0,
-                 tp_world: int = 1, fp8: bool = False, prefill_rowmajor: bool = True):
+                 tp_world: int = 1, fp8: bool = False, prefill_rowmajor: bool = True, w13: bool = True):
         """fp8: also hold the Gemma decoder linears as fp8 e4m3 with per-output-channel scales (`<name>8`,
         `<name>_s8` in each layer dict) for the PG_FP8 GEMMs of prefill and batch > 16 decode (BASELINE
-        configs[4]); the bf16 copies stay for the weight-streaming GEMV path (batch <= 16 decode)."""
+        configs[4]); the bf16 copies stay for the weight-streaming GEMV path (batch <= 16 decode).
+        w13: also hold the Gemma linears and the lm_head as the lossless 13-bit pack (`<name>_w13`, `lm_w13`;
+        frag13_pack) that the batch-1 decode GEMVs stream -- single rank, bf16 only; a matrix that does not pack has
+        no such entry and decodes from its `_w` form."""
         self.cfg = cfg
+        self.w13 = bool(w13) and int(tp_world) == 1 and not fp8
+        self._w13_missing = []
         self.fp8 = bool(fp8)
         self.prefill_rowmajor = bool(prefill_rowmajor)   # keep row-major Gemma linears beside the packed ones
         self.tp_rank, self.tp_world = int(tp_rank), int(tp_world)
@@ -167,6 +265,7 @@ class PackedWeights:
 
     def _pack_text(self, t, get, dev, bf, f32):
         # ---------------- Gemma
+        self.lm_w13 = None
         R, W = self.tp_rank, self.tp_world
         self.hidden = t["hidden_size"]
         self.heads_total = t["num_attention_heads"]
@@ -216,6 +315,7 @@ class PackedWeights:
             lm_w = torch.zeros(self.vocab_local_pad, self.hidden, dtype=torch.bfloat16, device=dev)
             lm_w[:vl] = self.embed[vo:vo + vl]
             self.lm_w = frag_pack(lm_w) if self.frag else lm_w
+            self.lm_w13 = self._pack13("lm_head", lm_w)
             del lm_w
             self.lm_bias = torch.zeros(self.vocab_local_pad, dtype=torch.float32, device=dev)
             self.lm_bias[:vl] = bias
@@ -245,6 +345,10 @@ class PackedWeights:
             layer = dict(
                 in_w=f32(get(lp + "input_layernorm.weight")), qkv_w=pk(qkv_w), o_w=pk(o_w),
                 post_w=f32(get(lp + "post_attention_layernorm.weight")), gu_w=pk(gu), down_w=pk(down))
+            for name, m in (("qkv", qkv_w), ("o", o_w), ("gu", gu), ("down", down)):
+                p13 = self._pack13(f"layer {i} {name}", m)
+                if p13 is not None:
+                    layer[name + "_w13"] = p13
             if self.frag and self.prefill_rowmajor and not self.fp8:
                 # row-major copies for the large-M prefill GEMMs: gemm256's LDS-DMA tile loads run 7-11%
                 # faster on them than on the fragment-packed image (scripts/tune/gemm_bench.py), and
@@ -271,6 +375,18 @@ class PackedWeights:
         self.final_w = f32(get(lm + "model.norm.weight"))
         self.wflag = 0x100 if self.frag else 0            # ops.W_FRAG for every Gemma linear
         self.qkv_n = (self.heads + 2 * self.kv_heads) * hd
+        if self._w13_missing:                             # once per model, not an error: those launches stay PG_W_FRAG
+            _log.info("pghip: no 13-bit pack for %s (exponent span or shape); they decode from the bf16 fragment pack",
+                      ", ".join(self._w13_missing))
+
+    def _pack13(self, what: str, m: torch.Tensor):
+        """The 13-bit pack of row-major `m`, or None (w13 off, matrices not fragment-packed, or it does not fit)."""
+        if not (self.w13 and self.frag):
+            return None
+        p13 = frag13_pack(m)
+        if p13 is None:
+            self._w13_missing.append(what)
+        return p13
 
     def nbytes(self) -> int:
         n = 0
