@@ -196,6 +196,26 @@ typedef struct PgFusedArgs {
  * with pro_mode 0, PG_EPI_F32 with pro_mode 4; anything else returns hipErrorInvalidValue. */
 #define PG_W_FRAG13 0x2000
 
+/* PG_W_FRAG12 (added under ABI 13; OR-ed into epi_flags together with PG_W_FRAG13, pghip/weights.py frag12_pack): the
+ * exponent-coded pack in its 12-bit form.  Blocks, lane ownership, sign/mantissa bytes, shape rules, accepted launches
+ * and results (bit-identical to PG_W_FRAG) are those of PG_W_FRAG13; what changes is how a block stores its codes.
+ * A block is NARROW when it holds no exponent field 0 and its largest field - its smallest <= 15: code = field - bias,
+ * 4 bits, bias = the smallest field.  Every other block is WIDE and keeps the 5-bit codes above (0 = field 0, c >= 1 =
+ * field bias + c, bias = base - 1); a matrix packs when every wide block's largest field - base <= 30.
+ * With B = N/16 * K/128 blocks and H wide ones, `W` points at
+ *   main   B * 3072 bytes; block (t, b) at (t * K/128 + b) * 3072:
+ *            [   0, 2048)  the sign/mantissa bytes, as PG_W_FRAG13
+ *            [2048, 3072)  lane L's code words q0..q3 at 2048 + 16L: pair P = 4(2h + s) + p has the low four bits of its
+ *                          o = 0 code in bits [4p, 4p + 4) and of its o = 1 code in bits [16 + 4p, 20 + 4p) of q[2h + s]
+ *   table  one little-endian uint32 per block, in block order, padded with zero bytes to a multiple of 256 bytes:
+ *            bias | zflag << 8 | wide << 9 | line << 10   (zflag: a wide block that holds a code 0)
+ *   heap   (H + 1) lines of 256 bytes: line 0 is zero and is the line of every narrow block; the k-th wide block, in
+ *            block order, names line k >= 1, which holds lane L's dword at 4L: bit 4 of pair P's o = 0 code in bit P,
+ *            of its o = 1 code in bit 16 + P.
+ * The kernel trusts the table's line numbers: hand it only a pack that frag12_pack (or an equal packer) produced.
+ * PG_W_FRAG12 without PG_W_FRAG13, or with PG_FP8, returns hipErrorInvalidValue. */
+#define PG_W_FRAG12 0x4000
+
 /* C = A[M][K] . W[N][K]^T with fused epilogue.  nn.Linear call sites: siglip.py:59-62,71-75,156,177-178,
  * 183-185; paligemma.py:57,64; gemma.py:205-207,212-218,255-259,274-278,356,484,523.  K % 32 == 0
  * (% 64 when M > 16), N % 4 == 0.  M <= 16 takes the weight-streaming GEMV path. */

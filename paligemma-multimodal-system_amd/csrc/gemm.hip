@@ -11,10 +11,12 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const float
   const bool n64 = (epi_flags & PG_TILE_N64) != 0;
   const int epi = epi_flags & 0xFF;
   const bool slot_rows = (epi_flags & PG_SLOT_ROWS) != 0;
-  const bool frag13 = (epi_flags & PG_W_FRAG13) != 0;
-  PG_REQUIRE((epi_flags & ~(0xFF | PG_W_FRAG | PG_FP8 | PG_TILE_M1 | PG_TILE_N64 | PG_SLOT_ROWS | PG_W_FRAG13)) == 0 &&
-             epi <= PG_EPI_F32_RES);
-  // the 13-bit pack: the batch-1 decode forms only, whole 128-k blocks per wave in every split
+  const bool frag13 = (epi_flags & PG_W_FRAG13) != 0;               // an exponent-coded pack ...
+  const bool frag12 = (epi_flags & PG_W_FRAG12) != 0;               // ... in its 12-bit form
+  PG_REQUIRE((epi_flags & ~(0xFF | PG_W_FRAG | PG_FP8 | PG_TILE_M1 | PG_TILE_N64 | PG_SLOT_ROWS | PG_W_FRAG13 |
+                            PG_W_FRAG12)) == 0 &&
+             epi <= PG_EPI_F32_RES && (frag13 || !frag12));
+  // the 13- and 12-bit packs: the batch-1 decode forms only, whole 128-k blocks per wave in every split
   if (frag13) {
     const int pm = fa ? fa->pro_mode : 0;
     PG_REQUIRE(!frag && !fp8 && !m1 && !n64 && W != nullptr && ((uintptr_t)W & 15) == 0 && M >= 1 && M <= 4 &&
@@ -122,7 +124,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const float
   }
   // M <= 16 -> the weight-streaming GEMV, else the tile GEMM; PG_W_FRAG only for the Gemma epilogues (the
   // launchers run the row-major form of the others)
-  const int rc = frag13  ? pg_dispatch_gemv13(epi, a, lda, W, K, ksplit, e, stream)
+  const int rc = frag13  ? pg_dispatch_gemv13(epi, frag12 ? 12 : 13, a, lda, W, K, ksplit, e, stream)
                  : M <= 16 ? pg_dispatch_gemv(epi, frag, a, lda, w, ldw, K, ksplit, e, stream)
                          : pg_dispatch_tile(epi, frag, false, a, lda, w, ldw, K, ksplit, e, stream, m1, n64);
   if (rc) return rc;

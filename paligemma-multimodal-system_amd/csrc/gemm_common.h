@@ -184,6 +184,8 @@ __device__ __forceinline__ f32x4 load4_guard(const float* __restrict__ p, int n0
 #define PG_SLOT_ROWS 0x1000  // PgFusedArgs.slot_dev is int32 [B], one word per batch row (include/pghip.h)
 #define PG_W_FRAG13 0x2000  // W is the 13-bit lossless fragment pack (include/pghip.h), batch-1 decode GEMVs only
 #define PG_F13_BLOCK 3328   // ... bytes of one 16-row x 128-k block
+#define PG_W_FRAG12 0x4000  // with PG_W_FRAG13: the pack is the 12-bit form (include/pghip.h), the same launches
+#define PG_F12_BLOCK 3072   // ... bytes of one block of its main array; a wide block's fifth code bits are 256 B more
 
 // fp8 GEMV: the wide form (x once per workgroup in LDS, waves split N), gemm_gemv8.hip; gemm.hip checks against it
 #ifndef PG_GEMV8_WIDE
@@ -473,8 +475,9 @@ int pg_dispatch_tile(int epi, bool frag, bool f8, const bf16_t* A, int lda, cons
 // gemm_gemv.hip: M <= 16, bf16
 int pg_dispatch_gemv(int epi, bool frag, const bf16_t* A, int lda, const bf16_t* W, int ldw, int K, int ksplit,
                      const EpiArgs& e, hipStream_t st);
-// ... PG_W_FRAG13 weights (M <= 4, the batch-1 decode forms only; gemm.hip checks the shape rules)
-int pg_dispatch_gemv13(int epi, const bf16_t* A, int lda, const void* W, int K, int ksplit, const EpiArgs& e,
+// ... PG_W_FRAG13 / PG_W_FRAG12 weights (bits = 13 / 12; M <= 4, the batch-1 decode forms only; gemm.hip checks the
+// shape rules)
+int pg_dispatch_gemv13(int epi, int bits, const bf16_t* A, int lda, const void* W, int K, int ksplit, const EpiArgs& e,
                        hipStream_t st);
 // gemm_gemv8.hip: M <= 32, fp8 fragment-packed W
 int pg_dispatch_gemv8(int epi, const uint8_t* X, int ldx, const uint8_t* W, int K, int ksplit, const EpiArgs& e,

@@ -382,6 +382,48 @@ __device__ __forceinline__ void decode13(const W13& b, unsigned bm, u32x4 (&op)[
   }
 }
 
+// PG_W_FRAG12 (FRAG == 3; include/pghip.h): the same block in 12 dwords per lane -- the sign/mantissa bytes and four
+// dwords of 4-bit codes -- plus, for a wide block only, the dword of its 5-bit codes' top bits from the heap (a narrow
+// block's c5 is the heap's shared line 0, loaded and never read)
+struct W12 {
+  u32x4 sm[2];
+  u32x4 cq;
+  unsigned c5;
+};
+// The block's four MFMA operands, as decode13.  MODE 0: narrow, exponent field = code + bias; 1: wide, 5-bit codes, no
+// code 0, field = code + bias; 2: wide with a code 0 (field 0, bias left out).  Wave-uniform, from the block's table word.
+template <int MODE>
+__device__ __forceinline__ void decode12(const W12& b, unsigned bias, u32x4 (&op)[2][2]) {
+  unsigned q[4] = {b.cq[0], b.cq[1], b.cq[2], b.cq[3]};
+  unsigned c5 = 0;
+  // (opaque copies, as in decode13: the shifts the three decodes share stay inside their branches)
+#pragma unroll
+  for (int d = 0; d < 4; ++d) asm volatile("" : "+v"(q[d]));
+  if constexpr (MODE > 0) {
+    c5 = b.c5;
+    asm volatile("" : "+v"(c5));
+  }
+  const unsigned badd = bias * 0x00800080u;             // bias << 7 in both halves (scalar)
+#pragma unroll
+  for (int P = 0; P < 16; ++P) {
+    // pair P = 4(2h + s) + p: its two 4-bit codes, nibble p of either half of q[2h + s], go to bits 7..10 and 23..26
+    const unsigned w = q[P >> 2];
+    unsigned e = ((P & 3) == 0 ? w << 7 : (P & 3) == 1 ? w << 3 : (P & 3) == 2 ? w >> 1 : w >> 5) & 0x07800780u;
+    if constexpr (MODE > 0)                             // ... and a wide block's fifth bits, c5 bits P and 16 + P, to 11 and 27
+      e |= (P < 11 ? c5 << (11 - P) : c5 >> (P - 11)) & 0x08000800u;
+    if constexpr (MODE == 2) {
+      const unsigned nz = ((e + 0x0f800f80u) >> 5) & 0x00800080u;   // 1 << 7 per half whose code is not 0
+      e += __umul24(nz, bias);
+    } else {
+      e += badd;
+    }
+    const int h = P >> 3, s = (P >> 2) & 1, p = P & 3;
+    const unsigned x = b.sm[h][p];
+    const unsigned d = __builtin_amdgcn_perm(x, x, s == 0 ? 0x02020000u : 0x03030101u);
+    op[h][s][p] = (d & 0x807f807fu) | e;
+  }
+}
+
 template <int EPI, int NT, int U, int DEPTH, int PRO, int FRAG, int CPW = 0>
 __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W,
                                           int ldw, int K, const EpiArgs& e, const GemvIdx gi) {
@@ -469,9 +511,84 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
   // contiguous elements.  x uses the same map, so the k order inside the MFMA is consistent either way.
   constexpr int S_STRIDE = PG_GEMV_CONTIG ? 32 : 8;
   const int LANE_OFF = PG_GEMV_CONTIG ? g * 8 : g * 8 * U;
-  u32x4 wb[FRAG == 2 ? 1 : DEPTH][NT][U];
+  u32x4 wb[FRAG >= 2 ? 1 : DEPTH][NT][U];
   u32x4 xb[DEPTH][U];
   W13 wc[FRAG == 2 ? DB : 1][NT];
+  // FRAG12: the ring, and the table words (bias | zflag << 8 | wide << 9 | heap slot << 10) of the wave's blocks as
+  // scalars -- all CPW / 2 of them in the straight-line forms (tw[t][i]), the ring's in the runtime loop (tw[t][d]).
+  // The straight-line forms load them here, ahead of every other load of the kernel: the fifth-plane addresses hang
+  // on them, and their round trip then runs beside the prologue's own instead of in front of the stream.
+  constexpr int NTW = CPW > 0 ? CPW / 2 : DB;
+  W12 wd[FRAG == 3 ? DB : 1][NT];
+  unsigned tw[FRAG == 3 ? NT : 1][FRAG == 3 ? NTW : 1];
+  unsigned twv[FRAG == 3 && CPW > 0 ? NT : 1][FRAG == 3 && CPW > 0 ? NTW : 1];
+  const char* const w12 = (const char*)W;
+  const size_t nblk12 = (size_t)(e.N >> 4) * (K >> 7);
+  const unsigned* const tab12 = (const unsigned*)(w12 + nblk12 * PG_F12_BLOCK);
+  const char* const heap12 = (const char*)tab12 + ((nblk12 * 4 + 255) & ~(size_t)255);
+  auto blk12 = [&](int t, int i) {
+    return (size_t)min(tile0 + t, (e.N >> 4) - 1) * (K >> 7) + ((c0 >> 3) + i) * 4 + wave;
+  };
+  if constexpr (FRAG == 3 && CPW > 0) {
+#pragma unroll
+    for (int i = 0; i < NTW; ++i)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) twv[t][i] = tab12[blk12(t, i)];
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // block i's twelve main dwords, three lane-linear loads per tile, where the 13-bit ring issues its four
+  auto loadm12 = [&](int i, W12 (&wv)[NT]) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const char* p = w12 + blk12(t, i) * PG_F12_BLOCK;
+      constexpr bool hot = ((PG_GEMV_HOT & 1) && EPI == PG_EPI_QKV_ROPE) || ((PG_GEMV_HOT & 2) && PRO == 2);
+      if constexpr (PG_GEMV_FRAG_NT && !hot) {
+        wv[t].sm[0] = __builtin_nontemporal_load((const u32x4*)p + lane);
+        wv[t].sm[1] = __builtin_nontemporal_load((const u32x4*)(p + 1024) + lane);
+        wv[t].cq = __builtin_nontemporal_load((const u32x4*)(p + 2048) + lane);
+      } else {
+        wv[t].sm[0] = ((const u32x4*)p)[lane];
+        wv[t].sm[1] = ((const u32x4*)(p + 1024))[lane];
+        wv[t].cq = ((const u32x4*)(p + 2048))[lane];
+      }
+    }
+  };
+  // ... and its fifth plane: the heap line its table word names, unconditionally -- a narrow block names line 0, which
+  // every block of the launch shares (cache-hot, no HBM bytes), so there is neither a branch nor a select here.  (A
+  // narrow block reading 256 bytes of its own codes instead, to spread the addresses, lost: DESIGN §A.)
+  auto load512 = [&](W12 (&wv)[NT], int k) {
+    if constexpr (FRAG == 3)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) wv[t].c5 = ((const unsigned*)(heap12 + (size_t)(tw[t][k] >> 10) * 256))[lane];
+  };
+  // the runtime loop has no fixed block list to fetch ahead: a block's table word loads with it and its fifth plane
+  // waits for that word (this form is the fallback for shapes off the decode's; it is not tuned)
+  auto loadw12 = [&](int i, int d, W12 (&wv)[NT]) {
+    loadm12(i, wv);
+    if constexpr (FRAG == 3)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) tw[t][d] = __builtin_amdgcn_readfirstlane(tab12[blk12(t, i)]);
+    load512(wv, d);
+  };
+  auto mfma12 = [&](const W12 (&wv)[NT], int k, const u32x4 (&x0)[U], const u32x4 (&x1)[U]) {
+    static_assert(FRAG != 3 || U == 2, "FRAG12 blocks are two 64-k chunks");
+    if constexpr (FRAG == 3)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      u32x4 op[2][2];
+      const unsigned w = tw[t][k];
+      const unsigned bias = w & 0xffu;
+      if (!(w & 0x200u)) decode12<0>(wv[t], bias, op);
+      else if (w & 0x100u) decode12<2>(wv[t], bias, op);
+      else decode12<1>(wv[t], bias, op);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+          acc[t] = mfma16(__builtin_bit_cast(bf16x8, op[h][s]), __builtin_bit_cast(bf16x8, h == 0 ? x0[s] : x1[s]),
+                          acc[t]);
+    }
+  };
   // block i of this wave: tile t's block (c0 / 8 + i) * 4 + wave, four lane-linear loads and the block's table word
   auto loadw13 = [&](int i, W13 (&wv)[NT]) {
     const int nblk = K >> 7;
@@ -579,10 +696,33 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
         // (sched_barrier: the blocks' loads stay in ring order, so block 0's MFMAs wait for block 0 alone)
         if (d < DB && (CPW > 0 ? d < CPW / 2 : d < nb)) loadw13(d, wc[d]);
         __builtin_amdgcn_sched_barrier(0);
+      } else if constexpr (FRAG == 3) {
+        if (d < DB && (CPW > 0 ? d < CPW / 2 : d < nb)) {
+          if constexpr (CPW > 0) loadm12(d, wd[d]);
+          else loadw12(d, d, wd[d]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
       } else {
         if (CPW > 0 ? d < CPW : d < mine) loadw(d, wb[d]);
       }
     }
+  }
+  // FRAG12, straight-line forms: the table words are due (they went out first); the ring's fifth planes follow its main
+  // loads, so a narrow block -- whose decode never reads c5 -- still waits for its own twelve dwords alone
+  auto fifth12 = [&]() {
+    if constexpr (FRAG == 3 && CPW > 0) {
+#pragma unroll
+      for (int i = 0; i < NTW; ++i)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) tw[t][i] = __builtin_amdgcn_readfirstlane(twv[t][i]);
+#pragma unroll
+      for (int d = 0; d < DB; ++d)
+        if (d < NTW) load512(wd[d], d);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  if constexpr (FRAG == 3 && CPW > 0) {
+    if (prew) fifth12();
   }
   if constexpr (STAGED) {
     float* scratch = (float*)(dyn_smem + (((size_t)M * (Kr + XPAD) * 2 + 15) & ~(size_t)15));
@@ -600,10 +740,23 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
         loadx(2 * d + 1, xb[2 * d + 1]);
       }
       __builtin_amdgcn_sched_barrier(0);
+    } else if constexpr (FRAG == 3) {
+      if (d < DB && (CPW > 0 ? d < CPW / 2 : d < nb)) {
+        if (!prew) {
+          if constexpr (CPW > 0) loadm12(d, wd[d]);
+          else loadw12(d, d, wd[d]);
+        }
+        loadx(2 * d, xb[2 * d]);
+        loadx(2 * d + 1, xb[2 * d + 1]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
     } else if (CPW > 0 ? d < CPW : d < mine) {
       if (!prew) loadw(d, wb[d]);
       loadx(d, xb[d]);
     }
+  }
+  if constexpr (FRAG == 3 && CPW > 0) {
+    if (!prew) fifth12();
   }
   // PG_EPI_F32_FIN: the residual rows and norm weights the tile's last-arriving split finalises are loaded now
   // (nothing else writes them in this launch), so the reducer's only round trip is the slab read
@@ -648,6 +801,35 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
         loadx(2 * (i + DB) + 1, xb[2 * d + 1]);
       }
       __builtin_amdgcn_sched_barrier(0);
+    }
+  } else if constexpr (FRAG == 3 && CPW > 0) {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < CPW / 2; ++i) {
+      const int d = i % DB;
+      mfma12(wd[d], i, xb[2 * d], xb[2 * d + 1]);
+      if (i + DB < CPW / 2) {
+        loadm12(i + DB, wd[d]);
+        load512(wd[d], i + DB);
+        loadx(2 * (i + DB), xb[2 * d]);
+        loadx(2 * (i + DB) + 1, xb[2 * d + 1]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  } else if constexpr (FRAG == 3) {
+    for (int base = 0; base < nb; base += DB) {
+#pragma unroll
+      for (int d = 0; d < DB; ++d) {
+        const int i = base + d;
+        if (i < nb) {
+          mfma12(wd[d], d, xb[2 * d], xb[2 * d + 1]);
+          if (i + DB < nb) {
+            loadw12(i + DB, d, wd[d]);
+            loadx(2 * (i + DB), xb[2 * d]);
+            loadx(2 * (i + DB) + 1, xb[2 * d + 1]);
+          }
+        }
+      }
     }
   } else if constexpr (FRAG == 2) {
     for (int base = 0; base < nb; base += DB) {
@@ -924,7 +1106,7 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
 // 122 VGPRs + 12 AGPRs, three waves; told, it fits 128 without a spill)
 template <int EPI, int NT, int U, int DEPTH, int PRO, int FRAG, int CPW = 0>
 __global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(FRAG == 2 && CPW > 0 && EPI == PG_EPI_BF16_GELU_MUL ? 4 : 1, 8)))
+__attribute__((amdgpu_waves_per_eu(FRAG >= 2 && CPW > 0 && EPI == PG_EPI_BF16_GELU_MUL ? 4 : 1, 8)))
 void gemv_kernel(const bf16_t* __restrict__ A, int lda,
                                                    const bf16_t* __restrict__ W, int ldw, int K, EpiArgs e) {
   gemv_body<EPI, NT, U, DEPTH, PRO, FRAG, CPW>(A, lda, W, ldw, K, e,
@@ -1010,9 +1192,10 @@ static void launch_gemv(const bf16_t* A, int lda, const bf16_t* W, int ldw, int 
   }
 }
 
-// PG_W_FRAG13: the batch-1 decode forms, each with the depth and tile count of its PG_W_FRAG twin (launch_gemv_pro at
-// M <= 4) -- here the two-tile lm_head form takes every N.  CPW 4 and 8 are the chunk counts the decode shapes hit.
-template <int EPI, int NT, int DEPTH, int PRO>
+// PG_W_FRAG13 / PG_W_FRAG12 (F = 2 / 3): the batch-1 decode forms, each with the depth and tile count of its PG_W_FRAG
+// twin (launch_gemv_pro at M <= 4) -- here the two-tile lm_head form takes every N.  CPW 4 and 8 are the chunk counts
+// the decode shapes hit.
+template <int EPI, int NT, int DEPTH, int PRO, int F>
 static void launch_gemv13(const bf16_t* A, int lda, const void* W, int K, int ksplit, const EpiArgs& e, hipStream_t st) {
   static_assert(DEPTH % 2 == 0, "whole blocks in flight");
   const int ntiles = e.N / 16;
@@ -1026,25 +1209,32 @@ static void launch_gemv13(const bf16_t* A, int lda, const void* W, int K, int ks
   const dim3 grid((ntiles + NT - 1) / NT, ksplit);
   const bf16_t* w = (const bf16_t*)W;
   switch (PG_GEMV_CPW ? per_z / 4 : 0) {
-    case 4: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, 2, 4>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
-    case 8: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, 2, 8>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
-    default: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, 2, 0>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
+    case 4: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, F, 4>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
+    case 8: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, F, 8>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
+    default: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, F, 0>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
   }
 }
 
-int pg_dispatch_gemv13(int epi, const bf16_t* A, int lda, const void* W, int K, int ksplit, const EpiArgs& e,
-                       hipStream_t st) {
+template <int F>
+static int dispatch_gemv13(int epi, const bf16_t* A, int lda, const void* W, int K, int ksplit, const EpiArgs& e,
+                           hipStream_t st) {
   const int pm = e.f.pro_mode;
   if (e.M > 4 || (K / 64) % (8 * ksplit)) return (int)hipErrorInvalidValue;
-  if (epi == PG_EPI_QKV_ROPE && pm == 1) launch_gemv13<PG_EPI_QKV_ROPE, 1, PG_GEMV_D1, 1>(A, lda, W, K, ksplit, e, st);
-  else if (epi == PG_EPI_FX_ADD && pm == 2) launch_gemv13<PG_EPI_FX_ADD, 1, PG_GEMV_D1, 2>(A, lda, W, K, ksplit, e, st);
-  else if (epi == PG_EPI_FX_ADD && pm == 0) launch_gemv13<PG_EPI_FX_ADD, 1, PG_GEMV_D1, 0>(A, lda, W, K, ksplit, e, st);
-  else if (epi == PG_EPI_F32_FIN && pm == 0) launch_gemv13<PG_EPI_F32_FIN, 1, PG_GEMV_D1, 0>(A, lda, W, K, ksplit, e, st);
+  if (epi == PG_EPI_QKV_ROPE && pm == 1) launch_gemv13<PG_EPI_QKV_ROPE, 1, PG_GEMV_D1, 1, F>(A, lda, W, K, ksplit, e, st);
+  else if (epi == PG_EPI_FX_ADD && pm == 2) launch_gemv13<PG_EPI_FX_ADD, 1, PG_GEMV_D1, 2, F>(A, lda, W, K, ksplit, e, st);
+  else if (epi == PG_EPI_FX_ADD && pm == 0) launch_gemv13<PG_EPI_FX_ADD, 1, PG_GEMV_D1, 0, F>(A, lda, W, K, ksplit, e, st);
+  else if (epi == PG_EPI_F32_FIN && pm == 0) launch_gemv13<PG_EPI_F32_FIN, 1, PG_GEMV_D1, 0, F>(A, lda, W, K, ksplit, e, st);
   else if (epi == PG_EPI_BF16_GELU_MUL && pm == 1)
-    launch_gemv13<PG_EPI_BF16_GELU_MUL, 2, PG_GEMV_D2, 1>(A, lda, W, K, ksplit, e, st);
-  else if (epi == PG_EPI_F32 && pm == 4) launch_gemv13<PG_EPI_F32, 2, PG_GEMV_LM_D, 4>(A, lda, W, K, ksplit, e, st);
+    launch_gemv13<PG_EPI_BF16_GELU_MUL, 2, PG_GEMV_D2, 1, F>(A, lda, W, K, ksplit, e, st);
+  else if (epi == PG_EPI_F32 && pm == 4) launch_gemv13<PG_EPI_F32, 2, PG_GEMV_LM_D, 4, F>(A, lda, W, K, ksplit, e, st);
   else return (int)hipErrorInvalidValue;
   return 0;
+}
+
+int pg_dispatch_gemv13(int epi, int bits, const bf16_t* A, int lda, const void* W, int K, int ksplit, const EpiArgs& e,
+                       hipStream_t st) {
+  return bits == 12 ? dispatch_gemv13<3>(epi, A, lda, W, K, ksplit, e, st)
+                    : dispatch_gemv13<2>(epi, A, lda, W, K, ksplit, e, st);
 }
 
 int pg_dispatch_gemv(int epi, bool frag, const bf16_t* A, int lda, const bf16_t* W, int ldw, int K, int ksplit,

@@ -194,6 +194,10 @@ class PaliGemmaEngine:
     # (measured, profiles/w13_kernel_stats_{parent,new}.csv: gate/up 22.4 -> 19.4 us, down 12.3 -> 10.8, the finalised
     # down 13.4 -> 12.8, lm_head 150.6 -> 127.4; q|k|v 4.8 -> 5.5 and o_proj 5.1 -> 5.3 lost and stay PG_W_FRAG)
     W13_FORMS = ("gu", "down", "lm")
+    # ... in the 12-bit form of that pack (weights.frag12_pack, PG_W_FRAG12: 4-bit codes where a block's exponents span
+    # at most 16 fields, the fifth bit plane of the others in a heap) for the launches PackedWeights holds that way
+    # (PackedWeights.w12_forms = weights.W12_FORMS; a matrix is held in one form only, so the switch is PackedWeights'
+    # w12 argument -- PG_W12=0 packs, and so launches, the 13-bit form throughout; W13 off turns both off)
 
     def __init__(self, cfg: dict, weights: PackedWeights, device="cuda", comm=None):
         self.cfg = cfg
@@ -883,7 +887,8 @@ class PaliGemmaEngine:
         p13 = d.get(name + "_w13")
         if (self.W13 and fx and p13 is not None and name in self.W13_FORMS and B <= self.FUSE_MAX_B and self.tp == 1
                 and (W.shape[1] // 64) % (8 * ksplit) == 0):
-            return p13, ops.W_FRAG13, dict(N=W.shape[0], K=W.shape[1])
+            f12 = ops.W_FRAG12 if name in getattr(self.w, "w12_forms", ()) else 0
+            return p13, ops.W_FRAG13 | f12, dict(N=W.shape[0], K=W.shape[1])
         return W, self.w.wflag, {}
 
     def _decode_layers_fin(self, st: dict, cache: KVStore, ws):

@@ -24,6 +24,7 @@ TILE_M1 = 0x400  # OR into epi: all 256..288 rows in one row tile (batch-1 prefi
 TILE_N64 = 0x800  # OR into epi: 64 x 64 output tiles (small-M prefill GEMMs, include/pghip.h PG_TILE_N64)
 SLOT_ROWS = 0x1000  # OR into epi: PgFusedArgs.slot_dev is int32 [B], one word per batch row (PG_SLOT_ROWS)
 W_FRAG13 = 0x2000  # OR into epi (gemm_fused, M <= 4): W is the lossless 13-bit pack (weights.frag13_pack, PG_W_FRAG13)
+W_FRAG12 = 0x4000  # OR into epi beside W_FRAG13: ... in its 12-bit form (weights.frag12_pack, PG_W_FRAG12)
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -195,12 +196,22 @@ def fused_args(**kw) -> "_lib.PgFusedArgs":
     return fa
 
 
+def _packed_len_ok(n: int, nblk: int, f12: bool) -> bool:
+    """Is n the byte length of an exponent-coded pack of nblk blocks?  13-bit: blocks and a uint16 table; 12-bit: the
+    main array, the uint32 table in whole 256-B lines, and a heap of at least the shared line (weights.frag12_size)."""
+    if not f12:
+        return n == nblk * 3330
+    fixed = nblk * 3072 + (nblk * 4 + 255) // 256 * 256 + 256
+    return n >= fixed and (n - fixed) % 256 == 0 and (n - fixed) // 256 <= nblk
+
+
 def gemm_fused(A: Optional[torch.Tensor], W: torch.Tensor, out: torch.Tensor, fa, *, epi: int = EPI_BF16,
                M: int, bias: Optional[torch.Tensor] = None, ksplit: int = 1, N: Optional[int] = None,
                ldc: Optional[int] = None, keep=None, K: Optional[int] = None) -> torch.Tensor:
     """pg_gemm_fused: the GEMM with a fused prologue (x produced in-kernel) and/or RoPE/KV epilogue.
     `fa` is a PgFusedArgs (see fused_args); `keep` holds tensors it points to alive for the call.
-    With W_FRAG13 in epi, W is the flat uint8 pack of weights.frag13_pack and N, K name the matrix it holds."""
+    With W_FRAG13 in epi, W is the flat uint8 pack of weights.frag13_pack (with W_FRAG12 beside it, of
+    weights.frag12_pack) and N, K name the matrix it holds."""
     if (epi & 0xFF) == EPI_FX_ADD:
         _chk(out, torch.int64, "out (the fixed-point accumulator)")
     if ldc is None:
@@ -208,7 +219,7 @@ def gemm_fused(A: Optional[torch.Tensor], W: torch.Tensor, out: torch.Tensor, fa
     if epi & W_FRAG13:
         _chk(W, torch.uint8, "W (13-bit pack)")
         if N is None or K is None or N % 16 or K % 128 or W.dim() != 1 or not W.is_contiguous() or \
-                W.numel() != (N // 16) * (K // 128) * 3330:
+                not _packed_len_ok(W.numel(), (N // 16) * (K // 128), bool(epi & W_FRAG12)):
             raise ValueError(f"pghip: a 13-bit packed W must be the flat pack of the [N][K] matrix named, got "
                              f"{tuple(W.shape)} for N={N} K={K}")
         _lib.call("pg_gemm_fused", _p(A), A.stride(0) if A is not None else K, _p(W), K, _p(bias), _p(out), ldc, M, N,

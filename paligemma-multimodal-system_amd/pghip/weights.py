@@ -31,6 +31,7 @@ completes; the embedding gather, RMSNorm weights and the vision tower stay repli
 from __future__ import annotations
 
 import logging
+import os
 
 import torch
 
@@ -163,6 +164,118 @@ def frag13_unpack(p: torch.Tensor, N: int, K: int) -> torch.Tensor:
     return torch.where(bits >= 32768, bits - 65536, bits).to(torch.int16).view(torch.bfloat16)
 
 
+F12_BLOCK = 3072     # bytes of one block in the 12-bit pack's main array: 64 lanes x (32 B sign/mantissa + 16 B codes)
+F12_LINE = 256       # ... and of one heap line: a wide block's fifth code bits, one dword per lane
+# the decode launches whose matrices PackedWeights holds in the 12-bit form (the others keep the 13-bit one): those whose
+# kernel beat its 13-bit twin by more than that kernel's own spread in the profile (the down projection
+# and the lm_head did not: §A)
+W12_FORMS = ("gu",)
+
+
+def frag12_size(N: int, K: int, wide: int) -> int:
+    """Bytes of the 12-bit pack of an [N][K] matrix with `wide` wide blocks: the main array, one uint32 per block
+    (padded to whole 256-B lines), and the heap's shared zero line plus one line per wide block."""
+    nblk = (N // 16) * (K // 128)
+    return nblk * F12_BLOCK + _rup(nblk * 4, F12_LINE) + (wide + 1) * F12_LINE
+
+
+def frag12_pack(w: torch.Tensor):
+    """Row-major bf16 W[N][K] (N % 16 == 0, K % 512 == 0) -> the lossless 12-bit pack of include/pghip.h PG_W_FRAG12 as a
+    flat uint8 tensor of frag12_size(N, K, wide blocks) bytes, or None exactly where frag13_pack gives None (a block's
+    exponent fields span more than 31 codes, or the shape has no whole blocks)."""
+    if w.dtype != torch.bfloat16 or w.dim() != 2:
+        raise TypeError("frag12_pack needs a 2-D bf16 matrix")
+    N, K = w.shape
+    if N % 16 or K % 512 or N == 0 or K == 0:
+        return None
+    nb = K // 128
+    mains, tabs, lines = [], [], []
+    nwide = 0
+    for t0 in range(0, N // 16, _F13_TILES):
+        b = _f13_blocks(w[16 * t0:16 * (t0 + _F13_TILES)])
+        T = b.shape[0]
+        b = b.reshape(T, nb // 4, 4, 2, 4, 16, 2, 4, 2)
+        E = (b >> 7) & 0xFF
+        sm = ((b >> 8) & 0x80) | (b & 0x7F)
+        Ef = E.reshape(T, nb, -1)
+        base = torch.where(Ef > 0, Ef, torch.full_like(Ef, 256)).amin(-1)
+        base = torch.where(base == 256, torch.ones_like(base), base)          # no non-zero field: every code is 0
+        top = Ef.amax(-1)
+        if bool(((top - base) > 30).any()):
+            return None
+        zflag = (Ef == 0).any(-1)
+        wide = zflag | ((top - base) > 15)
+        bias = base - wide.to(base.dtype)                                     # narrow: field = code + base
+        c = torch.where(E > 0, E - bias.view(T, nb // 4, 4, 1, 1, 1, 1, 1, 1), torch.zeros_like(E))
+        smb = sm.permute(0, 1, 2, 3, 4, 5, 7, 8, 6).reshape(T, nb, 2 * 1024).to(torch.uint8)
+        # codes: [T][ci][w] [g][r] [j = 2h + s] [p] [o]
+        cp = c.permute(0, 1, 2, 4, 5, 3, 6, 7, 8).reshape(T, nb, 64, 4, 4, 2).to(torch.int64)
+        q = torch.zeros(T, nb, 64, 4, dtype=torch.int64, device=w.device)
+        c5 = torch.zeros(T, nb, 64, dtype=torch.int64, device=w.device)
+        for p in range(4):
+            q |= ((cp[..., p, 0] & 15) << (4 * p)) | ((cp[..., p, 1] & 15) << (16 + 4 * p))
+            for j in range(4):
+                c5 |= ((cp[:, :, :, j, p, 0] >> 4) << (4 * j + p)) | ((cp[:, :, :, j, p, 1] >> 4) << (16 + 4 * j + p))
+        qb = torch.stack([(q >> (8 * i)) & 0xFF for i in range(4)], -1).to(torch.uint8)    # [T][nb][64][4][4 bytes]
+        mains.append(torch.cat([smb, qb.reshape(T, nb, 1024)], -1).reshape(-1))
+        wf = wide.reshape(-1)
+        line = torch.where(wf, nwide + torch.cumsum(wf.to(torch.int64), 0), torch.zeros_like(wf, dtype=torch.int64))
+        tb = bias.reshape(-1).to(torch.int64) | (zflag.reshape(-1).to(torch.int64) << 8) | (wf.to(torch.int64) << 9) | \
+            (line << 10)
+        tabs.append(torch.stack([(tb >> (8 * i)) & 0xFF for i in range(4)], -1).to(torch.uint8).reshape(-1))
+        c5b = torch.stack([(c5 >> (8 * i)) & 0xFF for i in range(4)], -1).to(torch.uint8).reshape(T * nb, F12_LINE)
+        lines.append(c5b[wf].reshape(-1))
+        nwide += int(wf.sum())
+        del b, E, sm, Ef, c, smb, cp, q, c5, qb, c5b
+    if nwide >= 1 << 22:
+        return None                                     # (the table's line field; 4M wide blocks is 8.6 G weights)
+    nblk = (N // 16) * nb
+    pad = torch.zeros(_rup(nblk * 4, F12_LINE) - nblk * 4 + F12_LINE, dtype=torch.uint8, device=w.device)
+    return torch.cat(mains + tabs + [pad] + lines)
+
+
+def frag12_table(p: torch.Tensor, N: int, K: int):
+    """The pack's table as int64 [N / 16][K / 128] tensors (bias, zflag, wide, line), and the heap's line count."""
+    T, nb = N // 16, K // 128
+    nblk = T * nb
+    if p.dtype != torch.uint8 or p.dim() != 1 or N % 16 or K % 512 or p.numel() < frag12_size(N, K, 0) or \
+            (p.numel() - frag12_size(N, K, 0)) % F12_LINE:
+        raise ValueError("not the 12-bit pack of an [N][K] matrix")
+    tb = p[nblk * F12_BLOCK:nblk * (F12_BLOCK + 4)].view(T, nb, 4).to(torch.int64)
+    tb = sum(tb[..., i] << (8 * i) for i in range(4))
+    nlines = (p.numel() - nblk * F12_BLOCK - _rup(nblk * 4, F12_LINE)) // F12_LINE
+    return tb & 0xFF, (tb >> 8) & 1, (tb >> 9) & 1, tb >> 10, nlines
+
+
+def frag12_unpack(p: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """Inverse of frag12_pack: the row-major bf16 [N][K] matrix, bit for bit."""
+    bias, _, wide, line, nlines = frag12_table(p, N, K)
+    if int(wide.sum()) + 1 != nlines or int(line.max()) >= nlines:
+        raise ValueError("frag12_unpack: the heap does not hold exactly the wide blocks")
+    T, nb = N // 16, K // 128
+    nblk = T * nb
+    blk = p[:nblk * F12_BLOCK].view(T, nb, F12_BLOCK).to(torch.int64)
+    heap = p[nblk * F12_BLOCK + _rup(nblk * 4, F12_LINE):].view(nlines, 64, 4).to(torch.int64)
+    c5 = sum(heap[..., i] << (8 * i) for i in range(4))[line.reshape(-1)].view(T, nb, 64)
+    sm = blk[..., :2048].reshape(T, nb, 2, 64, 4, 2, 2)                     # [h][lane][p][o][s]
+    qb = blk[..., 2048:].reshape(T, nb, 64, 4, 4)
+    q = sum(qb[..., i] << (8 * i) for i in range(4))                         # [T][nb][64][j]
+    c = torch.zeros(T, nb, 64, 4, 4, 2, dtype=torch.int64, device=p.device)  # [lane][j][p][o]
+    for pp in range(4):
+        for o in range(2):
+            c[..., pp, o] = (q >> (16 * o + 4 * pp)) & 15
+            for j in range(4):
+                c[:, :, :, j, pp, o] |= ((c5 >> (16 * o + 4 * j + pp)) & 1) << 4
+    wd = wide.view(T, nb, 1, 1, 1, 1).bool()
+    E = torch.where(wd & (c == 0), torch.zeros_like(c), c + bias.view(T, nb, 1, 1, 1, 1))
+    E = E.view(T, nb, 64, 2, 2, 4, 2).permute(0, 1, 3, 2, 5, 6, 4)           # [lane][h][s][p][o] -> [h][lane][p][o][s]
+    bits = ((sm & 0x80) << 8) | (E << 7) | (sm & 0x7F)
+    bits = bits.reshape(T, nb // 4, 4, 2, 4, 16, 4, 2, 2)
+    #        t  r  ci h  w  g  s  p  o
+    bits = bits.permute(0, 5, 1, 3, 2, 4, 8, 6, 7).reshape(N, K)
+    return torch.where(bits >= 32768, bits - 65536, bits).to(torch.int16).view(torch.bfloat16)
+
+
 def rope_row_perm(D: int) -> torch.Tensor:
     """Row order inside one D-wide head block for the fused RoPE epilogue: 16-row tile t holds
     dims 8t..8t+7 then D/2+8t..D/2+8t+7, so each lane's rotate_half partner is lane ^ 32."""
@@ -185,15 +298,22 @@ def quant_rows_fp8(w: torch.Tensor):
 
 class PackedWeights:
     def __init__(self, cfg: dict, get, device="cuda", parts=("vision", "proj", "text"), tp_rank: int = 0,
-                 tp_world: int = 1, fp8: bool = False, prefill_rowmajor: bool = True, w13: bool = True):
+                 tp_world: int = 1, fp8: bool = False, prefill_rowmajor: bool = True, w13: bool = True,
+                 w12=None):
         """fp8: also hold the Gemma decoder linears as fp8 e4m3 with per-output-channel scales (`<name>8`,
         `<name>_s8` in each layer dict) for the PG_FP8 GEMMs of prefill and batch > 16 decode (BASELINE
         configs[4]); the bf16 copies stay for the weight-streaming GEMV path (batch <= 16 decode).
         w13: also hold the Gemma linears and the lm_head as the lossless 13-bit pack (`<name>_w13`, `lm_w13`;
         frag13_pack) that the batch-1 decode GEMVs stream -- single rank, bf16 only; a matrix that does not pack has
-        no such entry and decodes from its `_w` form."""
+        no such entry and decodes from its `_w` form.
+        w12 (None: on unless PG_W12=0): the matrices of the launches in W12_FORMS are held in the 12-bit form of that
+        pack instead (frag12_pack, PG_W_FRAG13 | PG_W_FRAG12) -- under the same `_w13` keys, never both forms of one
+        matrix; `w12_forms` names those launches for the engine."""
         self.cfg = cfg
         self.w13 = bool(w13) and int(tp_world) == 1 and not fp8
+        if w12 is None:
+            w12 = os.environ.get("PG_W12", "1") != "0"
+        self.w12_forms = W12_FORMS if (w12 and self.w13) else ()
         self._w13_missing = []
         self.fp8 = bool(fp8)
         self.prefill_rowmajor = bool(prefill_rowmajor)   # keep row-major Gemma linears beside the packed ones
@@ -315,7 +435,7 @@ class PackedWeights:
             lm_w = torch.zeros(self.vocab_local_pad, self.hidden, dtype=torch.bfloat16, device=dev)
             lm_w[:vl] = self.embed[vo:vo + vl]
             self.lm_w = frag_pack(lm_w) if self.frag else lm_w
-            self.lm_w13 = self._pack13("lm_head", lm_w)
+            self.lm_w13 = self._pack13("lm_head", lm_w, "lm")
             del lm_w
             self.lm_bias = torch.zeros(self.vocab_local_pad, dtype=torch.float32, device=dev)
             self.lm_bias[:vl] = bias
@@ -346,7 +466,7 @@ class PackedWeights:
                 in_w=f32(get(lp + "input_layernorm.weight")), qkv_w=pk(qkv_w), o_w=pk(o_w),
                 post_w=f32(get(lp + "post_attention_layernorm.weight")), gu_w=pk(gu), down_w=pk(down))
             for name, m in (("qkv", qkv_w), ("o", o_w), ("gu", gu), ("down", down)):
-                p13 = self._pack13(f"layer {i} {name}", m)
+                p13 = self._pack13(f"layer {i} {name}", m, name)
                 if p13 is not None:
                     layer[name + "_w13"] = p13
             if self.frag and self.prefill_rowmajor and not self.fp8:
@@ -379,11 +499,12 @@ class PackedWeights:
             _log.info("pghip: no 13-bit pack for %s (exponent span or shape); they decode from the bf16 fragment pack",
                       ", ".join(self._w13_missing))
 
-    def _pack13(self, what: str, m: torch.Tensor):
-        """The 13-bit pack of row-major `m`, or None (w13 off, matrices not fragment-packed, or it does not fit)."""
+    def _pack13(self, what: str, m: torch.Tensor, form: str):
+        """The exponent-coded pack of row-major `m` -- 12-bit for a launch in w12_forms, else 13-bit -- or None (w13 off,
+        matrices not fragment-packed, or it does not fit)."""
         if not (self.w13 and self.frag):
             return None
-        p13 = frag13_pack(m)
+        p13 = frag12_pack(m) if form in self.w12_forms else frag13_pack(m)
         if p13 is None:
             self._w13_missing.append(what)
         return p13
