@@ -12,6 +12,15 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;    // 8-byte raw loa
 
 #define LDS_AS __attribute__((address_space(3)))
 
+// Batch-1 decode kernels that gain from it (the gate/up, down and lm_head GEMVs on the exponent-coded packs, the
+// argmax + embed finaliser) take a hot argument header: at most 14 leading pointer / scalar parameters -- what the
+// kernel needs to issue every load in front of its first wait -- which the kernarg preload (pghip/build.py
+// PRELOAD_SOURCES) puts into SGPRs before the wave starts (16 user SGPRs, two of them the kernarg pointer); the argument
+// struct stays the last parameter for everything else.  0 = struct-only signatures, nothing preloaded.
+#ifndef PG_KARG_HOT
+#define PG_KARG_HOT 1
+#endif
+
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 
 // round-to-nearest-even f32 -> bf16 (v_cvt_pk_bf16_f32 at -O3; keeps NaN a NaN)

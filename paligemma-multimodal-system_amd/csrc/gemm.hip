@@ -2,6 +2,10 @@
 // in gemm_tile.hip, gemm_gemv.hip and gemm_gemv8.hip (gemm_common.h).
 #include "gemm_common.h"
 
+// the boundary's argument struct and the kernels' own (ABI 13): the hot argument header of the batch-1 decode kernels
+// (PG_KARG_HOT) is filled beside them and changes neither
+static_assert(sizeof(PgFusedArgs) == 336 && sizeof(EpiArgs) == 408, "PgFusedArgs / EpiArgs layout (ABI 13)");
+
 static int gemm_impl(const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc,
                      int M, int N, int K, int epi_flags, int ksplit, const float* aux, int aux_rows, void* aux_out,
                      int aux_ld, int aux_n, const PgFusedArgs* fa, hipStream_t stream) {

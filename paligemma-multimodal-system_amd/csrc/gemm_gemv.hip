@@ -424,7 +424,11 @@ __device__ __forceinline__ void decode12(const W12& b, unsigned bias, u32x4 (&op
   }
 }
 
-template <int EPI, int NT, int U, int DEPTH, int PRO, int FRAG, int CPW = 0>
+// HOT (PG_KARG_HOT, gemv_hot_kernel): what the loads in front of the weight ring need arrives in SGPRs, the rest of e
+// in one batch of scalar loads whose wait must not land in front of the ring -- so PRO 4's sums of squares, which
+// only the epilogue consumes and whose addresses need e.f.ss_ld / ss_n, go out right after the ring's first fill
+// instead of before it.
+template <int EPI, int NT, int U, int DEPTH, int PRO, int FRAG, int CPW = 0, bool HOT = false>
 __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W,
                                           int ldw, int K, const EpiArgs& e, const GemvIdx gi) {
   constexpr int CH = U * 32;
@@ -476,7 +480,7 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
   float ssv[SSL];
 #pragma unroll
   for (int k = 0; k < SSL; ++k) ssv[k] = 0.f;
-  if constexpr (PRO == 4) {
+  auto load_ss = [&]() {
     if (wave == 0) {
       if (SS16 && M > 2) {
         const int rr = min(r, M - 1);
@@ -489,7 +493,8 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
         for (int k = 0; k < 4; ++k) ssv[k] = e.f.ss_in[(size_t)rr * e.f.ss_ld + min(lane % lpr + k * lpr, e.f.ss_n - 1)];
       }
     }
-  }
+  };
+  if constexpr (PRO == 4 && !HOT) load_ss();
   const bf16_t* xlds = xs + (xvalid ? r : M - 1) * (Kr + XPAD);
   // PG_EPI_QKV_ROPE: the epilogue's rotary positions and cache slot load before the weight stream, its cos/sin
   // right after the first chunks are issued, so the epilogue starts without a dependent round trip
@@ -758,6 +763,7 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
   if constexpr (FRAG == 3 && CPW > 0) {
     if (!prew) fifth12();
   }
+  if constexpr (PRO == 4 && HOT) load_ss();
   // PG_EPI_F32_FIN: the residual rows and norm weights the tile's last-arriving split finalises are loaded now
   // (nothing else writes them in this launch), so the reducer's only round trip is the slab read
   f32x4 fin_r[NT], fin_w[NT];
@@ -1107,10 +1113,61 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
 template <int EPI, int NT, int U, int DEPTH, int PRO, int FRAG, int CPW = 0>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(FRAG >= 2 && CPW > 0 && EPI == PG_EPI_BF16_GELU_MUL ? 4 : 1, 8)))
-void gemv_kernel(const bf16_t* __restrict__ A, int lda,
-                                                   const bf16_t* __restrict__ W, int ldw, int K, EpiArgs e) {
+void gemv_kernel(EpiArgs e, const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W, int ldw, int K) {
   gemv_body<EPI, NT, U, DEPTH, PRO, FRAG, CPW>(A, lda, W, ldw, K, e,
                                                GemvIdx{(int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y});
+}
+
+// PG_KARG_HOT: the batch-1 decode forms on the exponent-coded packs that gain from it (gate/up, down, the finalising
+// down, the lm_head: launch_gemv13) take a hot argument header, 14 dwords, 8-byte fields first so that no padding counts
+// against the preload: W, three pointers and a 64-bit word whose meaning the form fixes, N, K, mf = M | gridDim.y << 16
+// (the K split count, which the kernel otherwise reads from the dispatch's hidden arguments in front of everything
+// else), ldw.  In order of first use:
+//   PRO 1:     h0 = fx, h1 = resid_in, h2 = norm_w
+//   PRO 0 / 4: h0 = A, h2 = ss_in, x3 = lda
+// The header's fields overwrite their twins in a copy of e (registers: the copy is split field by field), so the body
+// reads one EpiArgs whichever signature brought it.  (gemv_kernel above takes its struct FIRST for the same reason
+// turned round: the preload stops at the first aggregate, so the forms that keep that signature -- q|k|v, which lost
+// 0.3 us a launch on a header, o_proj, which gained nothing, and every batched one -- run the entry code they had
+// before this source was compiled with the preload)
+template <int EPI, int NT, int U, int DEPTH, int PRO, int FRAG, int CPW = 0>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(FRAG >= 2 && CPW > 0 && EPI == PG_EPI_BF16_GELU_MUL ? 4 : 1, 8)))
+void gemv_hot_kernel(const bf16_t* __restrict__ W, const void* h0, const void* h1, const void* h2,
+                     unsigned long long x3, int N, int K, int mf, int ldw, const bf16_t* __restrict__ A, int lda,
+                     EpiArgs e) {
+  static_assert(PRO == 0 || PRO == 1 || PRO == 4, "forms with a header");
+  EpiArgs eh = e;
+  eh.N = N;
+  eh.M = mf & 0xffff;
+  if constexpr (PRO == 1) {
+    eh.f.fx = (long long*)h0;
+    eh.f.resid_in = (const float*)h1;
+    eh.f.norm_w = (const float*)h2;
+  } else {
+    A = (const bf16_t*)h0;
+    lda = (int)x3;
+    eh.f.ss_in = (const float*)h2;
+  }
+  gemv_body<EPI, NT, U, DEPTH, PRO, FRAG, CPW, true>(
+      A, lda, W, ldw, K, eh, GemvIdx{(int)blockIdx.x, (int)blockIdx.y, 0, (int)((unsigned)mf >> 16)});
+}
+
+// one launch of a gemv_kernel instantiation: HOT (and PG_KARG_HOT) fills the header from the same EpiArgs
+template <bool HOT, int EPI, int NT, int DEPTH, int PRO, int FRAG, int CPW>
+static void launch_gemv_one(dim3 grid, size_t lds, hipStream_t st, const bf16_t* A, int lda, const bf16_t* W, int ldw,
+                            int K, const EpiArgs& e) {
+  if constexpr (HOT && PG_KARG_HOT) {
+    const PgFusedArgs& f = e.f;
+    const void *h0 = nullptr, *h1 = nullptr, *h2 = nullptr;
+    unsigned long long x3 = 0;
+    if (PRO == 1) h0 = f.fx, h1 = f.resid_in, h2 = f.norm_w;
+    else h0 = A, h2 = f.ss_in, x3 = (unsigned)lda;
+    hipLaunchKernelGGL((gemv_hot_kernel<EPI, NT, 2, DEPTH, PRO, FRAG, CPW>), grid, dim3(256), lds, st, W, h0, h1, h2, x3,
+                       e.N, K, (int)(e.M | grid.y << 16), ldw, A, lda, e);
+  } else {
+    hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, FRAG, CPW>), grid, dim3(256), lds, st, e, A, lda, W, ldw, K);
+  }
 }
 
 // measured configs (round-1 GEMV sweep): M <= 4: one tile per WG, U=2, 8 chunks in flight;
@@ -1122,10 +1179,10 @@ static void launch_gemv_cpw(dim3 grid, size_t lds, hipStream_t st, const bf16_t*
   const int nch = K / 64;                              // U = 2: 64-element chunks
   const int cpw = (nch % ksplit == 0 && (nch / ksplit) % 4 == 0) ? nch / ksplit / 4 : 0;
   switch (PG_GEMV_CPW ? cpw : 0) {
-    case 4: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, FRAG, 4>), grid, dim3(256), lds, st, A, lda, W, ldw, K, e); break;
-    case 8: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, FRAG, 8>), grid, dim3(256), lds, st, A, lda, W, ldw, K, e); break;
-    case 16: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, FRAG, 16>), grid, dim3(256), lds, st, A, lda, W, ldw, K, e); break;
-    default: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, FRAG, 0>), grid, dim3(256), lds, st, A, lda, W, ldw, K, e); break;
+    case 4: launch_gemv_one<false, EPI, NT, DEPTH, PRO, FRAG, 4>(grid, lds, st, A, lda, W, ldw, K, e); break;
+    case 8: launch_gemv_one<false, EPI, NT, DEPTH, PRO, FRAG, 8>(grid, lds, st, A, lda, W, ldw, K, e); break;
+    case 16: launch_gemv_one<false, EPI, NT, DEPTH, PRO, FRAG, 16>(grid, lds, st, A, lda, W, ldw, K, e); break;
+    default: launch_gemv_one<false, EPI, NT, DEPTH, PRO, FRAG, 0>(grid, lds, st, A, lda, W, ldw, K, e); break;
   }
 }
 
@@ -1208,10 +1265,12 @@ static void launch_gemv13(const bf16_t* A, int lda, const void* W, int K, int ks
   }
   const dim3 grid((ntiles + NT - 1) / NT, ksplit);
   const bf16_t* w = (const bf16_t*)W;
+  // the hot argument header for the forms it gained on; q|k|v and o_proj keep the struct (§A)
+  constexpr bool HOT = PRO == 0 || PRO == 4 || EPI == PG_EPI_BF16_GELU_MUL;
   switch (PG_GEMV_CPW ? per_z / 4 : 0) {
-    case 4: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, F, 4>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
-    case 8: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, F, 8>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
-    default: hipLaunchKernelGGL((gemv_kernel<EPI, NT, 2, DEPTH, PRO, F, 0>), grid, dim3(256), lds, st, A, lda, w, K, K, e); break;
+    case 4: launch_gemv_one<HOT, EPI, NT, DEPTH, PRO, F, 4>(grid, lds, st, A, lda, w, K, K, e); break;
+    case 8: launch_gemv_one<HOT, EPI, NT, DEPTH, PRO, F, 8>(grid, lds, st, A, lda, w, K, K, e); break;
+    default: launch_gemv_one<HOT, EPI, NT, DEPTH, PRO, F, 0>(grid, lds, st, A, lda, w, K, K, e); break;
   }
 }
 

@@ -37,6 +37,13 @@ ARCH = os.environ.get("PGHIP_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-I", CSRC, "-I", INCLUDE,
          "-Wno-pass-failed"]
+# Leading scalar / pointer kernel parameters preloaded into SGPRs (up to 14 dwords; csrc/common.h PG_KARG_HOT), for the
+# sources whose batch-1 decode kernels were measured to gain from it.  Not a global flag: the short latency-bound
+# kernels (q|k|v, decode attention) ran 0.3 us a launch slower with it and a header, and no other
+# source's kernels were measured with it; the kernels of these two sources that keep the old entry take their argument
+# struct first, which the preload leaves alone.
+PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+PRELOAD_SOURCES = ("gemm_gemv.hip", "misc.hip")
 _MARK = b"PGHIP_SOURCE_HASH="
 
 
@@ -51,7 +58,7 @@ def _inputs():
 def _config() -> str:
     """The compile configuration without its machine-specific include paths (the GPU box holds the tree elsewhere)."""
     flags = [f for f in FLAGS if f not in (CSRC, INCLUDE)]
-    return " ".join([os.path.basename(HIPCC), *flags])
+    return " ".join([os.path.basename(HIPCC), *flags, *PRELOAD_FLAGS, "@", *PRELOAD_SOURCES])
 
 
 def _config_tag(defines=()) -> str:
@@ -95,7 +102,8 @@ def _obj_key(src: str, defines=()) -> str:
 
 
 def _compile(src: str, obj: str, defines=()) -> str:
-    cmd = [HIPCC, *FLAGS, *[f"-D{d}" for d in defines], "-c", src, "-o", obj + ".tmp"]
+    extra = PRELOAD_FLAGS if os.path.basename(src) in PRELOAD_SOURCES else []
+    cmd = [HIPCC, *FLAGS, *extra, *[f"-D{d}" for d in defines], "-c", src, "-o", obj + ".tmp"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed on {src}:\n{r.stderr}")
