@@ -46,6 +46,16 @@
 #ifndef PG_GEMV_LM_D
 #define PG_GEMV_LM_D 6    // ... and that form's chunks in flight
 #endif
+// PG_W_FRAG12 forms that read x straight from memory (down, the finalising down, the lm_head): the ring's first fill
+// goes out in two parts.  The first S blocks issue their main and x loads, then the table words (the kernel's oldest
+// loads) are waited for and those S blocks' fifth planes follow; every later block of the fill issues its fifth plane
+// with its own main loads, as a refill does.  A wide block of the fill then waits for the loads up to its own, not for
+// the whole fill (vmcnt retires in order).  0: every fifth plane behind the whole fill (the order before).  Measured
+// per kernel with S = 0 / 1 / 2 / 3: down 10.53 / 10.25 / 10.32 / 10.40 us, the lm_head 125.5 / 119.3 /
+// 119.7 / -.
+#ifndef PG_GEMV_W12_SPLIT
+#define PG_GEMV_W12_SPLIT 1
+#endif
 #ifndef PG_GEMV_FIN_NT
 #define PG_GEMV_FIN_NT 2  // (tuning) 16-column tiles per workgroup of the finalised batched (M > 4) GEMV: 2 or 4
 #endif
@@ -714,6 +724,11 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
   }
   // FRAG12, straight-line forms: the table words are due (they went out first); the ring's fifth planes follow its main
   // loads, so a narrow block -- whose decode never reads c5 -- still waits for its own twelve dwords alone
+  // (the forms without a prologue -- PG_GEMV_W12_SPLIT: only the fill's first S12 blocks take their fifth planes here,
+  // behind their own main loads; the fill's later blocks issue theirs with their main loads, the words being scalars by
+  // then)
+  constexpr int FILL12 = DB < NTW ? DB : NTW;   // blocks of the first fill
+  constexpr int S12 = (prew || PG_GEMV_W12_SPLIT <= 0 || PG_GEMV_W12_SPLIT > FILL12) ? FILL12 : PG_GEMV_W12_SPLIT;
   auto fifth12 = [&]() {
     if constexpr (FRAG == 3 && CPW > 0) {
 #pragma unroll
@@ -721,8 +736,13 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
 #pragma unroll
         for (int t = 0; t < NT; ++t) tw[t][i] = __builtin_amdgcn_readfirstlane(twv[t][i]);
 #pragma unroll
-      for (int d = 0; d < DB; ++d)
-        if (d < NTW) load512(wd[d], d);
+      for (int d = 0; d < S12; ++d) load512(wd[d], d);
+      // (without a prologue behind them nothing that may write memory follows these loads, and the compiler then sinks
+      // block 0's into the wide branch of block 0's decode, its only reader: issued there it is the kernel's youngest
+      // load, a full round trip behind a vmcnt(0).  The empty statement below may write the heap as far as the compiler
+      // knows -- it is handed the pointer, W being __restrict__ -- which pins the loads here; it emits nothing and
+      // waits for nothing.)
+      if constexpr (!prew) asm volatile("" ::"s"(heap12) : "memory");
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -748,20 +768,24 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
     } else if constexpr (FRAG == 3) {
       if (d < DB && (CPW > 0 ? d < CPW / 2 : d < nb)) {
         if (!prew) {
-          if constexpr (CPW > 0) loadm12(d, wd[d]);
-          else loadw12(d, d, wd[d]);
+          if constexpr (CPW > 0) {
+            loadm12(d, wd[d]);
+            if (d >= S12) load512(wd[d], d);
+          } else {
+            loadw12(d, d, wd[d]);
+          }
         }
         loadx(2 * d, xb[2 * d]);
         loadx(2 * d + 1, xb[2 * d + 1]);
       }
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (CPW > 0) {
+        if (!prew && d == S12 - 1) fifth12();
+      }
     } else if (CPW > 0 ? d < CPW : d < mine) {
       if (!prew) loadw(d, wb[d]);
       loadx(d, xb[d]);
     }
-  }
-  if constexpr (FRAG == 3 && CPW > 0) {
-    if (!prew) fifth12();
   }
   if constexpr (PRO == 4 && HOT) load_ss();
   // PG_EPI_F32_FIN: the residual rows and norm weights the tile's last-arriving split finalises are loaded now

@@ -167,9 +167,9 @@ def frag13_unpack(p: torch.Tensor, N: int, K: int) -> torch.Tensor:
 F12_BLOCK = 3072     # bytes of one block in the 12-bit pack's main array: 64 lanes x (32 B sign/mantissa + 16 B codes)
 F12_LINE = 256       # ... and of one heap line: a wide block's fifth code bits, one dword per lane
 # the decode launches whose matrices PackedWeights holds in the 12-bit form (the others keep the 13-bit one): those whose
-# kernel beat its 13-bit twin by more than that kernel's own spread in the profile (the down projection
-# and the lm_head did not: §A)
-W12_FORMS = ("gu",)
+# kernel beat its 13-bit twin by its bar in the profile (gate/up first; the down projection, its finalising
+# launch and the lm_head once their first fill issued the fifth planes in ring order)
+W12_FORMS = ("gu", "down", "lm")
 
 
 def frag12_size(N: int, K: int, wide: int) -> int:
