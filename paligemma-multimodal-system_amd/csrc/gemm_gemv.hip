@@ -1,5 +1,6 @@
-// bf16 decode GEMV (M <= 16): gemv_kernel and its launchers (see gemm_common.h).
-#include "gemm_common.h"
+// bf16 decode GEMV (M <= 16): gemv_kernel -- the weight ring and the epilogue -- and its launchers (see gemm_common.h);
+// the prologues and the 13- / 12-bit block decodes it calls are in gemv_parts.h.
+#include "gemv_parts.h"
 
 // --------------------------------------------------------------------------------------
 // Skinny GEMM / GEMV (M <= 16): weight streaming straight to VGPRs
@@ -17,34 +18,19 @@
 //   1: x = RMSNorm(resid_in + sum_s partials[s]) * (1 + w)       (GemmaRMSNorm, modeling_gemma.py:172-181)
 //      workgroup (0,0) also writes resid_out = resid_in + sum partials (ping-pong residual stream)
 //   2: x = merge of the split-KV attention partials (2^(m_s - M) weighted, / sum l)
-// For PRO != 0 the WG's K range of x is built in LDS (bf16, rows padded by 16 B against bank conflicts).
-#define XPAD 8
+//   3: x = resid * (1 + w), the row's rstd applied in the epilogue;  4: x rows read from A, rstd in the epilogue
+// For PRO 1, 2, 3 the WG's K range of x is built in LDS (XPAD, gemv_parts.h); the first weight chunks are issued before
+// that prologue.
 
-// tuning knobs (scripts/tune/): issue the first weight chunks before the prologue; one-pass online
-// merge of the split-KV partials in the attention-merge prologue
-#ifndef PG_GEMV_PREW
-#define PG_GEMV_PREW 1
-#endif
-#ifndef PG_GEMV_NT
-#define PG_GEMV_NT 0
-#endif
-#ifndef PG_GEMV_CONTIG
-#define PG_GEMV_CONTIG 0
-#endif
-#ifndef PG_GEMV_QKV_NT1
-#define PG_GEMV_QKV_NT1 1   // batched (M > 4) q|k|v GEMV with one 16-row tile per workgroup
+// tuning knobs (scripts/tune/build_variant.py -D...); every choice that is no longer a knob has its row in DESIGN §A
+#ifndef PG_GEMV_D1
+#define PG_GEMV_D1 8      // chunks in flight of the one-tile GEMV (M <= 4: batch-1 decode o / down / q|k|v / lm_head)
 #endif
 #ifndef PG_GEMV_D2
-#define PG_GEMV_D2 4
-#endif
-// (round 5: the gate/up GEMV at batch 1 with two gate/up pairs per workgroup -- half the workgroups re-reading the row
-// -- measured slower, 1.061 vs 1.059 ms/token at 3 chunks in flight, 1.073 at 2: profiles/r05_gateup_nt4_ab.jsonl)
-#ifndef PG_GEMV_LM_NT
-#define PG_GEMV_LM_NT 2   // the batch-1..4 lm_head GEMV with two 16-row tiles per workgroup (1: one; 2 with 6 chunks in
-                          // flight: -5.5 us per token, 4 chunks: -3.5, profiles/r05_lm_head_nt2_ab.jsonl)
+#define PG_GEMV_D2 4      // ... of the two-tile GEMV (M > 4 and the gate/up pair) and of the batched one-tile q|k|v
 #endif
 #ifndef PG_GEMV_LM_D
-#define PG_GEMV_LM_D 6    // ... and that form's chunks in flight
+#define PG_GEMV_LM_D 6    // ... of the batch-1..4 lm_head GEMV with two 16-row tiles per workgroup (launch_gemv_pro)
 #endif
 // PG_W_FRAG12 forms that read x straight from memory (down, the finalising down, the lm_head): the ring's first fill
 // goes out in two parts.  The first S blocks issue their main and x loads, then the table words (the kernel's oldest
@@ -56,384 +42,11 @@
 #ifndef PG_GEMV_W12_SPLIT
 #define PG_GEMV_W12_SPLIT 1
 #endif
-#ifndef PG_GEMV_FIN_NT
-#define PG_GEMV_FIN_NT 2  // (tuning) 16-column tiles per workgroup of the finalised batched (M > 4) GEMV: 2 or 4
-#endif
-#ifndef PG_GEMV_D1
-#define PG_GEMV_D1 8      // chunks in flight of the one-tile GEMV (M <= 4: batch-1 decode o / down / q|k|v / lm_head)
-#endif
-#ifndef PG_GEMV_XLDS
-#define PG_GEMV_XLDS 0
-#endif
-#ifndef PG_GEMV_HOT
-#define PG_GEMV_HOT 1           // 1 = q|k|v, 2 = o_proj (merge prologue), 3 = both read their weights with
-                                // default-policy loads (allocating in the Infinity Cache) while the others stay nt:
-                                // the 18 layers' q|k|v (189 MB) then stay on-die across decode steps; pt-224 B=1
-                                // A/B/A/B 1.1348/1.1363 -> 1.1325/1.1314 ms/token (2: neutral; 3: 1.142, they no
-                                // longer fit; scripts/r02/gpu_s3f.sh)
-#endif
-#ifndef PG_GEMV_FRAG_NT
-#define PG_GEMV_FRAG_NT 1
-#endif
-#ifndef PG_GEMV_CPW
-#define PG_GEMV_CPW 1     // decode GEMV: straight-line chunk loop when every wave owns the same chunk count
-#endif
-
-// the GEMV's workgroup coordinates (blockIdx / gridDim of its launch)
-struct GemvIdx {
-  int bx, by, nx, ny;
-};
-
-#ifndef PG_GEMV_PRO_EARLY
-#define PG_GEMV_PRO_EARLY 2     // 2: the q|k|v GEMV at M == 1; 1: gate/up too (152 VGPRs: 3 waves/SIMD, level); 0: off
-                                // (measured and removed: the same loads as LDS DMA, slower; the o_proj merge prologue's
-                                // partials loaded early, level -- profiles/r05_decode_early_prologue_ab.jsonl)
-#endif
-// A workgroup barrier that orders LDS only: the wave's LDS ops are waited for, its global loads (the weight ring) stay
-// in flight (__syncthreads' fence would wait for them too: s_waitcnt vmcnt(0))
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
-// The batch-1 RMSNorm prologue in two halves (PRO 1, M == 1, K <= 2048): the loads -- thread t owns the float4s
-// c = t and t + 256 of the row, the residual's and the norm weight's, the fixed-point accumulator's raw words --
-// and, after the weight ring is issued, the sum of squares, the normalisation and the LDS image.
-struct Pro1Row {
-  f32x4 a[2], w[2];
-  i64x2 qa[2], qb[2];
-};
-__device__ __forceinline__ void pro1_row_load(const PgFusedArgs& f, int K, Pro1Row& p) {
-  const int t = threadIdx.x, K4 = K >> 2;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = t + i * 256;
-    p.a[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    p.w[i] = p.a[i];
-    p.qa[i] = i64x2{0, 0};
-    p.qb[i] = p.qa[i];
-    if (c < K4) {
-      p.w[i] = ((const f32x4*)f.norm_w)[c];
-      if (f.resid_in) p.a[i] = ((const f32x4*)f.resid_in)[c];
-      if (f.fx) {
-        p.qa[i] = *(const i64x2*)(f.fx + 4 * c);
-        p.qb[i] = *(const i64x2*)(f.fx + 4 * c + 2);
-      }
-    }
-  }
-}
-__device__ __forceinline__ void pro1_row_finish(const PgFusedArgs& f, int K, const Pro1Row& p, bf16_t* xs,
-                                                float* red) {
-  const int t = threadIdx.x, K4 = K >> 2;
-  f32x4 v[2];
-  float ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    v[i] = p.a[i];
-    if (f.fx) v[i] += f32x4{fx_to_f32(p.qa[i][0]), fx_to_f32(p.qa[i][1]), fx_to_f32(p.qb[i][0]), fx_to_f32(p.qb[i][1])};
-    ss += v[i][0] * v[i][0] + v[i][1] * v[i][1] + v[i][2] * v[i][2] + v[i][3] * v[i][3];
-  }
-  ss = wave_sum(ss);
-  if ((t & 63) == 0) red[t >> 6] = ss;
-  lds_barrier();
-  const float rstd = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + f.eps);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = t + i * 256;
-    if (c < K4) {
-      const f32x4 w = p.w[i];
-      u32x2 pk;
-      pk[0] = pack_bf2((v[i][0] * rstd) * (1.0f + w[0]), (v[i][1] * rstd) * (1.0f + w[1]));
-      pk[1] = pack_bf2((v[i][2] * rstd) * (1.0f + w[2]), (v[i][3] * rstd) * (1.0f + w[3]));
-      *(u32x2*)(xs + c * 4) = pk;
-    }
-  }
-  lds_barrier();
-}
-
-template <int PRO>
-__device__ __forceinline__ void gemv_prologue(const EpiArgs& e, int M, int K, int k0, int Kr, bf16_t* xs,
-                                              float* scratch, const bf16_t* __restrict__ A, int lda,
-                                              const GemvIdx& gi) {
-  const PgFusedArgs& f = e.f;
-  const int t = threadIdx.x;
-  const int ldx = Kr + XPAD;
-  if constexpr (PRO == 0 || PRO == 4) {
-    // x rows [M][k0, k0 + Kr) copied from A into LDS (PG_GEMV_XLDS): one L2 read per workgroup
-    const int K8 = Kr >> 3;
-    for (int idx = t; idx < M * K8; idx += 256) {
-      const int m = idx / K8, c = idx % K8;
-      *(u32x4*)(xs + m * ldx + c * 8) = *(const u32x4*)(A + (size_t)m * lda + k0 + c * 8);
-    }
-  } else if constexpr (PRO == 1) {
-    // RMSNorm over the FULL row (Kr == K): pass 1 sum of squares, pass 2 normalise into LDS
-    const int K4 = K >> 2;
-    const bool w0 = gi.bx == 0 && gi.by == 0 && f.resid_out != nullptr;
-    float* red = scratch;   // [4 waves][16 rows]
-    if (M == 1 && K4 <= 4 * 256) {
-      // one row: keep it in registers between the two passes (one dependent round trip fewer)
-      f32x4 v[4], wn[4];
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int c = t + i * 256;
-        v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (c < K4) {
-          wn[i] = ((const f32x4*)f.norm_w)[c];          // issued with the residual: one round trip
-          f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (f.resid_in) a = ((const f32x4*)f.resid_in)[c];
-          if (f.fx) a += fx_load4(f.fx + 4 * c);
-          for (int sp = 0; sp < f.nsplit; ++sp) a += ((const f32x4*)(f.partials + (size_t)sp * K))[c];
-          v[i] = a;
-          ss += a[0] * a[0] + a[1] * a[1] + a[2] * a[2] + a[3] * a[3];
-          if (w0) ((f32x4*)f.resid_out)[c] = a;
-        }
-      }
-      ss = wave_sum(ss);
-      if ((t & 63) == 0) red[t >> 6] = ss;
-      __syncthreads();
-      const float rstd = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + f.eps);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int c = t + i * 256;
-        if (c < K4) {
-          const f32x4 w = wn[i];
-          u32x2 pk;
-          pk[0] = pack_bf2((v[i][0] * rstd) * (1.0f + w[0]), (v[i][1] * rstd) * (1.0f + w[1]));
-          pk[1] = pack_bf2((v[i][2] * rstd) * (1.0f + w[2]), (v[i][3] * rstd) * (1.0f + w[3]));
-          *(u32x2*)(xs + c * 4) = pk;
-        }
-      }
-      __syncthreads();
-      return;
-    }
-    for (int m = 0; m < M; ++m) {
-      float ss = 0.f;
-      for (int c = t; c < K4; c += 256) {
-        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (f.resid_in) v = ((const f32x4*)(f.resid_in + (size_t)m * K))[c];
-        if (f.fx) v += fx_load4(f.fx + (size_t)m * K + 4 * c);
-        for (int sp = 0; sp < f.nsplit; ++sp) v += ((const f32x4*)(f.partials + ((size_t)sp * M + m) * K))[c];
-        ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-        if (w0) ((f32x4*)(f.resid_out + (size_t)m * K))[c] = v;
-      }
-      ss = wave_sum(ss);
-      if ((t & 63) == 0) red[(t >> 6) * 16 + m] = ss;
-    }
-    __syncthreads();
-    for (int m = 0; m < M; ++m) {
-      const float rstd = rsqrtf((red[m] + red[16 + m] + red[32 + m] + red[48 + m]) / (float)K + f.eps);
-      for (int c = t; c < K4; c += 256) {
-        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (f.resid_in) v = ((const f32x4*)(f.resid_in + (size_t)m * K))[c];
-        if (f.fx) v += fx_load4(f.fx + (size_t)m * K + 4 * c);
-        for (int sp = 0; sp < f.nsplit; ++sp) v += ((const f32x4*)(f.partials + ((size_t)sp * M + m) * K))[c];
-        const f32x4 w = ((const f32x4*)f.norm_w)[c];
-        u32x2 pk;
-        pk[0] = pack_bf2((v[0] * rstd) * (1.0f + w[0]), (v[1] * rstd) * (1.0f + w[1]));
-        pk[1] = pack_bf2((v[2] * rstd) * (1.0f + w[2]), (v[3] * rstd) * (1.0f + w[3]));
-        *(u32x2*)(xs + m * ldx + c * 4) = pk;
-      }
-    }
-  } else if constexpr (PRO == 3) {
-    // x = resid * (1 + w) over the full row (the residual was finalised by the producer's FIN epilogue);
-    // per-row rstd from the producer's per-tile sums of squares, applied in the epilogue (scratch[64 + m])
-    const int K4 = K >> 2;
-    float* red = scratch;   // [4 waves][16 rows], then rstd [16] at +64
-    for (int m = 0; m < M; ++m) {
-      for (int c = t; c < K4; c += 256) {
-        const f32x4 v = ((const f32x4*)(f.resid_in + (size_t)m * K))[c];
-        const f32x4 w = ((const f32x4*)f.norm_w)[c];
-        u32x2 pk;
-        pk[0] = pack_bf2(v[0] * (1.0f + w[0]), v[1] * (1.0f + w[1]));
-        pk[1] = pack_bf2(v[2] * (1.0f + w[2]), v[3] * (1.0f + w[3]));
-        *(u32x2*)(xs + m * ldx + c * 4) = pk;
-      }
-      float ssum = 0.f;
-      for (int i = t; i < f.ss_n; i += 256) ssum += f.ss_in[(size_t)m * f.ss_ld + i];
-      ssum = wave_sum(ssum);
-      if ((t & 63) == 0) red[(t >> 6) * 16 + m] = ssum;
-    }
-    __syncthreads();
-    if (t < M) red[64 + t] = rsqrtf((red[t] + red[16 + t] + red[32 + t] + red[48 + t]) / (float)K + f.eps);
-  } else if constexpr (PRO == 2) {
-    // one pass per (row, head, 4 dims): merge over the splits, no LDS staging / barriers
-    const int D = f.head_dim, G = f.q_per_kv, S = f.asplit;
-    const int h0 = k0 / D, nh = Kr / D, D4 = D >> 2;
-    const int items = M * nh * D4;
-    if (S <= 16) {
-      // every split's (m, l, o) loaded at once (one dependent L2 round trip, no read of the kv length:
-      // splits past it hold m = -inf and weigh 0), then a two-pass max / weighted sum
-      for (int idx = t; idx < M * nh * D4; idx += 256) {
-        const int m = idx / (nh * D4), rem = idx % (nh * D4), hl = rem / D4, d4 = rem % D4;
-        const int hq = h0 + hl;
-        const long base0 = (((long)m * f.kv_heads + hq / G) * S) * 16 + (hq % G);
-        float ms[16], ls[16];
-        f32x4 o4[16];
-        f32x2 mlv[16];
-        // all 32 loads issued back to back before any is used (sched_barrier): the scheduler otherwise recycled
-        // one register for six of the O loads, a load -> wait -> load chain of six round trips
-#pragma unroll
-        for (int sp = 0; sp < 16; ++sp) {
-          const long bs = base0 + (long)min(sp, S - 1) * 16;
-          mlv[sp] = *(const f32x2*)(f.part_ml + bs * 2);
-          o4[sp] = *(const f32x4*)(f.part_o + bs * f.dtw + d4 * 4);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int sp = 0; sp < 16; ++sp) {
-          ms[sp] = sp < S ? mlv[sp][0] : -INFINITY;
-          ls[sp] = mlv[sp][1];
-        }
-        float mx = ms[0];
-#pragma unroll
-        for (int sp = 1; sp < 16; ++sp) mx = fmaxf(mx, ms[sp]);
-        float den = 0.f;
-        f32x4 num = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int sp = 0; sp < 16; ++sp) {
-          const float w = ms[sp] == -INFINITY ? 0.f : exp2f(ms[sp] - mx);
-          den += w * ls[sp];
-          num += w * o4[sp];
-        }
-        const float inv = 1.0f / den;
-        u32x2 pk;
-        pk[0] = pack_bf2(num[0] * inv, num[1] * inv);
-        pk[1] = pack_bf2(num[2] * inv, num[3] * inv);
-        *(u32x2*)(xs + m * ldx + hl * D + d4 * 4) = pk;
-      }
-      __syncthreads();
-      return;
-    }
-    const int Seff = (f.slot_dev && f.akeys > 0) ? min(S, (*f.slot_dev + f.akeys) / f.akeys) : S;
-    // one (row, head, 4 dims) item merged over its first Sn splits
-    auto merge_item = [&](int idx, int m, int Sn) {
-      const int rem = idx % (nh * D4), hl = rem / D4, d4 = rem % D4;
-      const int hq = h0 + hl;
-      const long base0 = (((long)m * f.kv_heads + hq / G) * S) * 16 + (hq % G);
-      float mx = -INFINITY, den = 0.f;
-      f32x4 num = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-      for (int sp = 0; sp < Sn; ++sp) {
-        const long bs = base0 + (long)sp * 16;
-        const float ms = f.part_ml[bs * 2], ls = f.part_ml[bs * 2 + 1];
-        const f32x4 o4 = *(const f32x4*)(f.part_o + bs * f.dtw + d4 * 4);
-        const float mn = fmaxf(mx, ms);
-        const float ca = mx == -INFINITY ? 0.f : exp2f(mx - mn);
-        const float cb = ms == -INFINITY ? 0.f : exp2f(ms - mn);
-        den = den * ca + cb * ls;
-        num = num * ca + cb * o4;
-        mx = mn;
-      }
-      const float inv = 1.0f / den;
-      u32x2 pk;
-      pk[0] = pack_bf2(num[0] * inv, num[1] * inv);
-      pk[1] = pack_bf2(num[2] * inv, num[3] * inv);
-      *(u32x2*)(xs + m * ldx + hl * D + d4 * 4) = pk;
-    };
-    if (e.slot_rows) {
-      // PG_SLOT_ROWS: row m's own count, its kv length before this token being slot_dev[m] + slot_base (a branch on
-      // a kernel argument: the shared-length loop below keeps its wave-uniform trip count)
-      for (int idx = t; idx < items; idx += 256) {
-        const int m = idx / (nh * D4);
-        merge_item(idx, m, min(S, (f.slot_dev[m] + f.slot_base + f.akeys) / f.akeys));
-      }
-    } else {
-      for (int idx = t; idx < items; idx += 256) merge_item(idx, idx / (nh * D4), Seff);
-    }
-  }
-  __syncthreads();
-}
 
 // CPW > 0: every wave owns exactly CPW chunks (launch checks K / CH / ksplit == 4 * CPW).  The chunk loop is then
 // straight-line code with unconditional loads, so hipcc's s_waitcnt bookkeeping stays exact: each chunk's MFMAs
 // wait only for that chunk (vmcnt(N), N = younger loads), instead of the conservative vmcnt(0) that the runtime
 // loop and its exec-masked loads produce at every ring turn (the ring drained before its first MFMA).
-// PG_W_FRAG13 (FRAG == 2; include/pghip.h): one lane's share of a 16-row x 128-k block, 13 dwords for 32 weights -- the
-// sign/mantissa bytes of the block's two 64-k chunks, the 5-bit exponent codes, and the block's base | zflag << 8 word
-struct W13 {
-  u32x4 sm[2];
-  u32x4 cq;
-  unsigned c4;
-  unsigned bz;
-};
-// The block's four MFMA operands op[h][s], bit for bit the u32x4 pieces the PG_W_FRAG layout holds for chunk h, piece
-// s.  Z: the block holds a code 0 (exponent field 0: no base added to that weight); wave-uniform, from the base table.
-template <bool Z>
-__device__ __forceinline__ void decode13(const W13& b, unsigned bm, u32x4 (&op)[2][2]) {
-  unsigned q[5] = {b.cq[0], b.cq[1], b.cq[2], b.cq[3], b.c4};
-  // (opaque copies: the compiler otherwise hoists the 20 shifts both decodes share above their branch and keeps them
-  // live across it -- 12 to 20 more VGPRs per kernel, one wave per SIMD fewer on q|k|v and the finalised down)
-#pragma unroll
-  for (int d = 0; d < 5; ++d) asm volatile("" : "+v"(q[d]));
-  const unsigned badd = bm * 0x00800080u;              // (base - 1) << 7 in both halves (scalar)
-#pragma unroll
-  for (int P = 0; P < 16; ++P) {
-    // the pair's two codes at bits 7..11 and 23..27, the exponent field's place in a bf16 pair
-    unsigned e;
-    if (P < 15) {
-      const unsigned w = q[P / 3];
-      e = (P % 3 == 0 ? w << 7 : P % 3 == 1 ? w << 2 : w >> 3) & 0x0f800f80u;
-    } else {
-      e = ((q[0] >> 8) & 0x00800080u) | ((q[1] >> 7) & 0x01000100u) | ((q[2] >> 6) & 0x02000200u) |
-          ((q[3] >> 5) & 0x04000400u) | ((q[4] >> 4) & 0x08000800u);
-    }
-    if constexpr (Z) {
-      const unsigned nz = ((e + 0x0f800f80u) >> 5) & 0x00800080u;   // 1 << 7 per half whose code is not 0
-      e += __umul24(nz, bm);
-    } else {
-      e += badd;
-    }
-    const int h = P >> 3, s = (P >> 2) & 1, p = P & 3;
-    // sm dword p = bytes (s 0, o 0), (s 1, o 0), (s 0, o 1), (s 1, o 1): each byte doubled into its half-word puts the
-    // sign at bit 15 and the mantissa at bits 0..6 (one v_perm), the rest is masked off as the exponent goes in
-    const unsigned x = b.sm[h][p];
-    const unsigned d = __builtin_amdgcn_perm(x, x, s == 0 ? 0x02020000u : 0x03030101u);
-    op[h][s][p] = (d & 0x807f807fu) | e;
-  }
-}
-
-// PG_W_FRAG12 (FRAG == 3; include/pghip.h): the same block in 12 dwords per lane -- the sign/mantissa bytes and four
-// dwords of 4-bit codes -- plus, for a wide block only, the dword of its 5-bit codes' top bits from the heap (a narrow
-// block's c5 is the heap's shared line 0, loaded and never read)
-struct W12 {
-  u32x4 sm[2];
-  u32x4 cq;
-  unsigned c5;
-};
-// The block's four MFMA operands, as decode13.  MODE 0: narrow, exponent field = code + bias; 1: wide, 5-bit codes, no
-// code 0, field = code + bias; 2: wide with a code 0 (field 0, bias left out).  Wave-uniform, from the block's table word.
-template <int MODE>
-__device__ __forceinline__ void decode12(const W12& b, unsigned bias, u32x4 (&op)[2][2]) {
-  unsigned q[4] = {b.cq[0], b.cq[1], b.cq[2], b.cq[3]};
-  unsigned c5 = 0;
-  // (opaque copies, as in decode13: the shifts the three decodes share stay inside their branches)
-#pragma unroll
-  for (int d = 0; d < 4; ++d) asm volatile("" : "+v"(q[d]));
-  if constexpr (MODE > 0) {
-    c5 = b.c5;
-    asm volatile("" : "+v"(c5));
-  }
-  const unsigned badd = bias * 0x00800080u;             // bias << 7 in both halves (scalar)
-#pragma unroll
-  for (int P = 0; P < 16; ++P) {
-    // pair P = 4(2h + s) + p: its two 4-bit codes, nibble p of either half of q[2h + s], go to bits 7..10 and 23..26
-    const unsigned w = q[P >> 2];
-    unsigned e = ((P & 3) == 0 ? w << 7 : (P & 3) == 1 ? w << 3 : (P & 3) == 2 ? w >> 1 : w >> 5) & 0x07800780u;
-    if constexpr (MODE > 0)                             // ... and a wide block's fifth bits, c5 bits P and 16 + P, to 11 and 27
-      e |= (P < 11 ? c5 << (11 - P) : c5 >> (P - 11)) & 0x08000800u;
-    if constexpr (MODE == 2) {
-      const unsigned nz = ((e + 0x0f800f80u) >> 5) & 0x00800080u;   // 1 << 7 per half whose code is not 0
-      e += __umul24(nz, bias);
-    } else {
-      e += badd;
-    }
-    const int h = P >> 3, s = (P >> 2) & 1, p = P & 3;
-    const unsigned x = b.sm[h][p];
-    const unsigned d = __builtin_amdgcn_perm(x, x, s == 0 ? 0x02020000u : 0x03030101u);
-    op[h][s][p] = (d & 0x807f807fu) | e;
-  }
-}
-
 // HOT (PG_KARG_HOT, gemv_hot_kernel): what the loads in front of the weight ring need arrives in SGPRs, the rest of e
 // in one batch of scalar loads whose wait must not land in front of the ring -- so PRO 4's sums of squares, which
 // only the epilogue consumes and whose addresses need e.f.ss_ld / ss_n, go out right after the ring's first fill
@@ -521,11 +134,18 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
     rope_slot_raw = __hip_atomic_load(slot_p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 
-  // element offset of a lane's 16-B piece s inside a CH-element chunk: PG_GEMV_CONTIG lays piece s of the 4
-  // lane groups side by side (one load instruction = 64 contiguous bytes per row); otherwise a lane owns 16U
-  // contiguous elements.  x uses the same map, so the k order inside the MFMA is consistent either way.
-  constexpr int S_STRIDE = PG_GEMV_CONTIG ? 32 : 8;
-  const int LANE_OFF = PG_GEMV_CONTIG ? g * 8 : g * 8 * U;
+  // element offset of a lane's 16-B piece s inside a CH-element chunk: a lane owns 16U contiguous elements.  x uses
+  // the same map, so the k order inside the MFMA is consistent.
+  constexpr int S_STRIDE = 8;
+  const int LANE_OFF = g * 8 * U;
+  // The packed layouts' weights are read once, so non-temporal (measured: gate/up 28.7 -> 23.0 us, down 17.0 -> 13.8 us
+  // vs row-major plain loads) -- but for q|k|v, whose loads keep the default policy and allocate in the Infinity Cache:
+  // the 18 layers' q|k|v (189 MB) then stay on-die across decode steps.
+  constexpr bool hot = EPI == PG_EPI_QKV_ROPE;
+  auto wload = [&](const auto* p) {
+    if constexpr (hot) return *p;
+    else return __builtin_nontemporal_load(p);
+  };
   u32x4 wb[FRAG >= 2 ? 1 : DEPTH][NT][U];
   u32x4 xb[DEPTH][U];
   W13 wc[FRAG == 2 ? DB : 1][NT];
@@ -551,22 +171,16 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
       for (int t = 0; t < NT; ++t) twv[t][i] = tab12[blk12(t, i)];
     __builtin_amdgcn_sched_barrier(0);
   }
+  // the three planes both packs share, lane-linear: the block's sign/mantissa bytes and its first four code dwords
+  auto load_main = [&](const char* p, u32x4 (&sm)[2], u32x4& cq) {
+    sm[0] = wload((const u32x4*)p + lane);
+    sm[1] = wload((const u32x4*)(p + 1024) + lane);
+    cq = wload((const u32x4*)(p + 2048) + lane);
+  };
   // block i's twelve main dwords, three lane-linear loads per tile, where the 13-bit ring issues its four
   auto loadm12 = [&](int i, W12 (&wv)[NT]) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const char* p = w12 + blk12(t, i) * PG_F12_BLOCK;
-      constexpr bool hot = ((PG_GEMV_HOT & 1) && EPI == PG_EPI_QKV_ROPE) || ((PG_GEMV_HOT & 2) && PRO == 2);
-      if constexpr (PG_GEMV_FRAG_NT && !hot) {
-        wv[t].sm[0] = __builtin_nontemporal_load((const u32x4*)p + lane);
-        wv[t].sm[1] = __builtin_nontemporal_load((const u32x4*)(p + 1024) + lane);
-        wv[t].cq = __builtin_nontemporal_load((const u32x4*)(p + 2048) + lane);
-      } else {
-        wv[t].sm[0] = ((const u32x4*)p)[lane];
-        wv[t].sm[1] = ((const u32x4*)(p + 1024))[lane];
-        wv[t].cq = ((const u32x4*)(p + 2048))[lane];
-      }
-    }
+    for (int t = 0; t < NT; ++t) load_main(w12 + blk12(t, i) * PG_F12_BLOCK, wv[t].sm, wv[t].cq);
   };
   // ... and its fifth plane: the heap line its table word names, unconditionally -- a narrow block names line 0, which
   // every block of the launch shares (cache-hot, no HBM bytes), so there is neither a branch nor a select here.  (A
@@ -585,6 +199,30 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
       for (int t = 0; t < NT; ++t) tw[t][d] = __builtin_amdgcn_readfirstlane(tab12[blk12(t, i)]);
     load512(wv, d);
   };
+  // block i of this wave: tile t's block (c0 / 8 + i) * 4 + wave, four lane-linear loads and the block's table word
+  auto loadw13 = [&](int i, W13 (&wv)[NT]) {
+    const int nblk = K >> 7;
+    const int bk = ((c0 >> 3) + i) * 4 + wave;
+    const char* w13 = (const char*)W;
+    const unsigned short* tab = (const unsigned short*)(w13 + (size_t)(e.N >> 4) * nblk * PG_F13_BLOCK);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const size_t blk = (size_t)min(tile0 + t, (e.N >> 4) - 1) * nblk + bk;
+      const char* p = w13 + blk * PG_F13_BLOCK;
+      load_main(p, wv[t].sm, wv[t].cq);
+      wv[t].c4 = wload((const unsigned*)(p + 3072) + lane);
+      wv[t].bz = tab[blk];
+    }
+  };
+  // a decoded block's four MFMAs into tile t's accumulator, in the PG_W_FRAG order (chunk, piece)
+  auto mfma4 = [&](int t, const u32x4 (&op)[2][2], const u32x4 (&x0)[U], const u32x4 (&x1)[U]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+        acc[t] = mfma16(__builtin_bit_cast(bf16x8, op[h][s]), __builtin_bit_cast(bf16x8, h == 0 ? x0[s] : x1[s]),
+                        acc[t]);
+  };
   auto mfma12 = [&](const W12 (&wv)[NT], int k, const u32x4 (&x0)[U], const u32x4 (&x1)[U]) {
     static_assert(FRAG != 3 || U == 2, "FRAG12 blocks are two 64-k chunks");
     if constexpr (FRAG == 3)
@@ -596,37 +234,7 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
       if (!(w & 0x200u)) decode12<0>(wv[t], bias, op);
       else if (w & 0x100u) decode12<2>(wv[t], bias, op);
       else decode12<1>(wv[t], bias, op);
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-          acc[t] = mfma16(__builtin_bit_cast(bf16x8, op[h][s]), __builtin_bit_cast(bf16x8, h == 0 ? x0[s] : x1[s]),
-                          acc[t]);
-    }
-  };
-  // block i of this wave: tile t's block (c0 / 8 + i) * 4 + wave, four lane-linear loads and the block's table word
-  auto loadw13 = [&](int i, W13 (&wv)[NT]) {
-    const int nblk = K >> 7;
-    const int bk = ((c0 >> 3) + i) * 4 + wave;
-    const char* w13 = (const char*)W;
-    const unsigned short* tab = (const unsigned short*)(w13 + (size_t)(e.N >> 4) * nblk * PG_F13_BLOCK);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const size_t blk = (size_t)min(tile0 + t, (e.N >> 4) - 1) * nblk + bk;
-      const char* p = w13 + blk * PG_F13_BLOCK;
-      constexpr bool hot = ((PG_GEMV_HOT & 1) && EPI == PG_EPI_QKV_ROPE) || ((PG_GEMV_HOT & 2) && PRO == 2);
-      if constexpr (PG_GEMV_FRAG_NT && !hot) {
-        wv[t].sm[0] = __builtin_nontemporal_load((const u32x4*)p + lane);
-        wv[t].sm[1] = __builtin_nontemporal_load((const u32x4*)(p + 1024) + lane);
-        wv[t].cq = __builtin_nontemporal_load((const u32x4*)(p + 2048) + lane);
-        wv[t].c4 = __builtin_nontemporal_load((const unsigned*)(p + 3072) + lane);
-      } else {
-        wv[t].sm[0] = ((const u32x4*)p)[lane];
-        wv[t].sm[1] = ((const u32x4*)(p + 1024))[lane];
-        wv[t].cq = ((const u32x4*)(p + 2048))[lane];
-        wv[t].c4 = ((const unsigned*)(p + 3072))[lane];
-      }
-      wv[t].bz = tab[blk];
+      mfma4(t, op, x0, x1);
     }
   };
   // block i's 2 x U x NT MFMAs in the PG_W_FRAG order (chunk, piece, tile); the decode is register-only on both sides
@@ -641,47 +249,29 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
       const unsigned bm = (bz & 0xffu) - 1u;
       if (bz & 0x100u) decode13<true>(wv[t], bm, op);
       else decode13<false>(wv[t], bm, op);
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-          acc[t] = mfma16(__builtin_bit_cast(bf16x8, op[h][s]), __builtin_bit_cast(bf16x8, h == 0 ? x0[s] : x1[s]),
-                          acc[t]);
+      mfma4(t, op, x0, x1);
     }
   };
   auto loadw = [&](int j, u32x4 (&wv)[NT][U]) {
     if constexpr (FRAG) {
-      // fragment-packed weights: tile t's chunk c is U wave-instructions of 1 KiB, lane-linear; read once,
-      // so non-temporal (measured: gate/up 28.7 -> 23.0 us, down 17.0 -> 13.8 us vs row-major plain loads)
+      // fragment-packed weights: tile t's chunk c is U wave-instructions of 1 KiB, lane-linear
       const int cc = c0 + wave + j * 4;
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int s = 0; s < U; ++s) {
-          const u32x4* src = (const u32x4*)(wfrag[t] + ((size_t)cc * U + s) * 512 + lane * 8);
-          constexpr bool hot = ((PG_GEMV_HOT & 1) && EPI == PG_EPI_QKV_ROPE) || ((PG_GEMV_HOT & 2) && PRO == 2);
-          if constexpr (PG_GEMV_FRAG_NT && !hot)
-            wv[t][s] = __builtin_nontemporal_load(src);
-          else
-            wv[t][s] = *src;
-        }
+        for (int s = 0; s < U; ++s) wv[t][s] = wload((const u32x4*)(wfrag[t] + ((size_t)cc * U + s) * 512 + lane * 8));
     } else {
       const int off = (c0 + wave + j * 4) * CH + LANE_OFF;
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int s = 0; s < U; ++s) {
-#if PG_GEMV_NT
-          wv[t][s] = __builtin_nontemporal_load((const u32x4*)(wrow[t] + off + S_STRIDE * s));
-#else
-          wv[t][s] = *(const u32x4*)(wrow[t] + off + S_STRIDE * s);
-#endif
-        }
+        for (int s = 0; s < U; ++s) wv[t][s] = *(const u32x4*)(wrow[t] + off + S_STRIDE * s);
     }
   };
+  constexpr bool STAGED = PRO != 0 && PRO != 4;   // x built in LDS by a prologue
   auto loadx = [&](int j, u32x4 (&xv)[U]) {
     const int koff = (wave + j * 4) * CH + LANE_OFF;      // offset inside this split
-    if constexpr ((PRO == 0 || PRO == 4) && !PG_GEMV_XLDS) {
+    if constexpr (!STAGED) {
 #pragma unroll
       for (int s = 0; s < U; ++s)
         xv[s] = *(const u32x4*)(xrow + c0 * CH + koff + S_STRIDE * s);
@@ -690,35 +280,52 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
       for (int s = 0; s < U; ++s) xv[s] = *(const u32x4*)(xlds + koff + S_STRIDE * s);
     }
   };
-  constexpr bool STAGED = (PRO != 0 && PRO != 4) || PG_GEMV_XLDS;   // x built in LDS by a prologue
-  // PRO 1 on one row of at most 2048 elements (batch-1 decode q|k|v and gate/up): the RMSNorm's loads go out BEFORE
-  // the weight ring and are held in registers, so they return first and the normalisation runs while the weights
-  // stream (issued after the ring, the prologue's loads made it wait for the whole ring: vmcnt counts in order)
-  const bool early = PRO == 1 && (PG_GEMV_PRO_EARLY == 1 || (PG_GEMV_PRO_EARLY == 2 && EPI == PG_EPI_QKV_ROPE)) &&
-                     M == 1 && (K >> 2) <= 512 && e.f.nsplit == 0 &&
+  // The ring of a 13- / 12-bit pack: block i (the chunk pair 2i, 2i + 1) into slot d as a refill issues it, and the
+  // MFMAs of the block in slot d
+  auto refill_blk = [&](int i, int d) {
+    if constexpr (FRAG == 2) {
+      loadw13(i, wc[d]);
+    } else if constexpr (CPW > 0) {
+      loadm12(i, wd[d]);
+      load512(wd[d], i);
+    } else {
+      loadw12(i, d, wd[d]);
+    }
+    loadx(2 * i, xb[2 * d]);
+    loadx(2 * i + 1, xb[2 * d + 1]);
+  };
+  auto mfma_blk = [&](int i, int d) {
+    if constexpr (FRAG == 2) mfma13(wc[d], xb[2 * d], xb[2 * d + 1]);
+    else mfma12(wd[d], CPW > 0 ? i : d, xb[2 * d], xb[2 * d + 1]);
+  };
+  // PRO 1 on one row of at most 2048 elements (batch-1 decode q|k|v): the RMSNorm's loads go out BEFORE the weight ring
+  // and are held in registers, so they return first and the normalisation runs while the weights stream (issued after
+  // the ring, the prologue's loads made it wait for the whole ring: vmcnt counts in order).  q|k|v only: gate/up too
+  // took 152 VGPRs, 3 waves/SIMD, and measured level (profiles/r05_decode_early_prologue_ab.jsonl).
+  const bool early = PRO == 1 && EPI == PG_EPI_QKV_ROPE && M == 1 && (K >> 2) <= 512 && e.f.nsplit == 0 &&
                      e.f.resid_out == nullptr;
   Pro1Row p1;
-  if constexpr (PRO == 1 && PG_GEMV_PRO_EARLY) {
+  if constexpr (PRO == 1) {
     if (early) pro1_row_load(e.f, K, p1);
     __builtin_amdgcn_sched_barrier(0);         // (the prologue's loads stay ahead of the ring in the vmcnt order)
   }
   // weights issued before the prologue (its loads are the critical path: the stream overlaps them)
-  constexpr bool prew = STAGED && PG_GEMV_PREW;
+  constexpr bool prew = STAGED;
   if (prew) {
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {
       if constexpr (FRAG == 2) {
         // (sched_barrier: the blocks' loads stay in ring order, so block 0's MFMAs wait for block 0 alone)
-        if (d < DB && (CPW > 0 ? d < CPW / 2 : d < nb)) loadw13(d, wc[d]);
+        if (d < DB && d < nb) loadw13(d, wc[d]);
         __builtin_amdgcn_sched_barrier(0);
       } else if constexpr (FRAG == 3) {
-        if (d < DB && (CPW > 0 ? d < CPW / 2 : d < nb)) {
+        if (d < DB && d < nb) {
           if constexpr (CPW > 0) loadm12(d, wd[d]);
           else loadw12(d, d, wd[d]);
         }
         __builtin_amdgcn_sched_barrier(0);
       } else {
-        if (CPW > 0 ? d < CPW : d < mine) loadw(d, wb[d]);
+        if (d < mine) loadw(d, wb[d]);
       }
     }
   }
@@ -750,23 +357,23 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
     if (prew) fifth12();
   }
   if constexpr (STAGED) {
-    float* scratch = (float*)(dyn_smem + (((size_t)M * (Kr + XPAD) * 2 + 15) & ~(size_t)15));
-    if (PRO == 1 && PG_GEMV_PRO_EARLY && early)
+    float* scratch = (float*)(dyn_smem + gemv_xs_bytes(M, Kr));
+    if (PRO == 1 && early)
       pro1_row_finish(e.f, K, p1, xs, scratch);
     else
-      gemv_prologue<PRO>(e, M, K, c0 * CH, nch * CH, xs, scratch, A, lda, gi);
+      gemv_prologue<PRO>(e, M, K, c0 * CH, nch * CH, xs, scratch, gi);
   }
 #pragma unroll
   for (int d = 0; d < DEPTH; ++d) {
     if constexpr (FRAG == 2) {
-      if (d < DB && (CPW > 0 ? d < CPW / 2 : d < nb)) {
+      if (d < DB && d < nb) {
         if (!prew) loadw13(d, wc[d]);
         loadx(2 * d, xb[2 * d]);
         loadx(2 * d + 1, xb[2 * d + 1]);
       }
       __builtin_amdgcn_sched_barrier(0);
     } else if constexpr (FRAG == 3) {
-      if (d < DB && (CPW > 0 ? d < CPW / 2 : d < nb)) {
+      if (d < DB && d < nb) {
         if (!prew) {
           if constexpr (CPW > 0) {
             loadm12(d, wd[d]);
@@ -782,7 +389,7 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
       if constexpr (CPW > 0) {
         if (!prew && d == S12 - 1) fifth12();
       }
-    } else if (CPW > 0 ? d < CPW : d < mine) {
+    } else if (d < mine) {
       if (!prew) loadw(d, wb[d]);
       loadx(d, xb[d]);
     }
@@ -819,60 +426,23 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
       rope_sn[t] = *(const f32x4*)(e.f.sin_t + off);
     }
   }
-  if constexpr (FRAG == 2 && CPW > 0) {
+  if constexpr (FRAG >= 2 && CPW > 0) {
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < CPW / 2; ++i) {
       const int d = i % DB;
-      mfma13(wc[d], xb[2 * d], xb[2 * d + 1]);
-      if (i + DB < CPW / 2) {
-        loadw13(i + DB, wc[d]);
-        loadx(2 * (i + DB), xb[2 * d]);
-        loadx(2 * (i + DB) + 1, xb[2 * d + 1]);
-      }
+      mfma_blk(i, d);
+      if (i + DB < CPW / 2) refill_blk(i + DB, d);
       __builtin_amdgcn_sched_barrier(0);
     }
-  } else if constexpr (FRAG == 3 && CPW > 0) {
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < CPW / 2; ++i) {
-      const int d = i % DB;
-      mfma12(wd[d], i, xb[2 * d], xb[2 * d + 1]);
-      if (i + DB < CPW / 2) {
-        loadm12(i + DB, wd[d]);
-        load512(wd[d], i + DB);
-        loadx(2 * (i + DB), xb[2 * d]);
-        loadx(2 * (i + DB) + 1, xb[2 * d + 1]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  } else if constexpr (FRAG == 3) {
+  } else if constexpr (FRAG >= 2) {
     for (int base = 0; base < nb; base += DB) {
 #pragma unroll
       for (int d = 0; d < DB; ++d) {
         const int i = base + d;
         if (i < nb) {
-          mfma12(wd[d], d, xb[2 * d], xb[2 * d + 1]);
-          if (i + DB < nb) {
-            loadw12(i + DB, d, wd[d]);
-            loadx(2 * (i + DB), xb[2 * d]);
-            loadx(2 * (i + DB) + 1, xb[2 * d + 1]);
-          }
-        }
-      }
-    }
-  } else if constexpr (FRAG == 2) {
-    for (int base = 0; base < nb; base += DB) {
-#pragma unroll
-      for (int d = 0; d < DB; ++d) {
-        const int i = base + d;
-        if (i < nb) {
-          mfma13(wc[d], xb[2 * d], xb[2 * d + 1]);
-          if (i + DB < nb) {
-            loadw13(i + DB, wc[d]);
-            loadx(2 * (i + DB), xb[2 * d]);
-            loadx(2 * (i + DB) + 1, xb[2 * d + 1]);
-          }
+          mfma_blk(i, d);
+          if (i + DB < nb) refill_blk(i + DB, d);
         }
       }
     }
@@ -932,7 +502,7 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
   const int m = r;
   const int q = 4 * g;
   if constexpr (PRO == 3) {
-    const float* scratch = (const float*)(dyn_smem + (((size_t)M * (Kr + XPAD) * 2 + 15) & ~(size_t)15));
+    const float* scratch = (const float*)(dyn_smem + gemv_xs_bytes(M, Kr));
     const float rs = scratch[64 + (m < M ? m : 0)];
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] *= rs;
@@ -1194,65 +764,63 @@ static void launch_gemv_one(dim3 grid, size_t lds, hipStream_t st, const bf16_t*
   }
 }
 
-// measured configs (round-1 GEMV sweep): M <= 4: one tile per WG, U=2, 8 chunks in flight;
-// M > 4 and the gate/up pair: two tiles per WG, U=2, 4 chunks in flight.
-// one gemv_kernel launch with the chunks-per-wave specialisation when the K split is exact (see gemv_kernel)
-template <int EPI, int NT, int DEPTH, int PRO, bool FRAG>
-static void launch_gemv_cpw(dim3 grid, size_t lds, hipStream_t st, const bf16_t* A, int lda, const bf16_t* W, int ldw,
-                            int K, int ksplit, const EpiArgs& e) {
-  const int nch = K / 64;                              // U = 2: 64-element chunks
-  const int cpw = (nch % ksplit == 0 && (nch / ksplit) % 4 == 0) ? nch / ksplit / 4 : 0;
-  switch (PG_GEMV_CPW ? cpw : 0) {
-    case 4: launch_gemv_one<false, EPI, NT, DEPTH, PRO, FRAG, 4>(grid, lds, st, A, lda, W, ldw, K, e); break;
-    case 8: launch_gemv_one<false, EPI, NT, DEPTH, PRO, FRAG, 8>(grid, lds, st, A, lda, W, ldw, K, e); break;
-    case 16: launch_gemv_one<false, EPI, NT, DEPTH, PRO, FRAG, 16>(grid, lds, st, A, lda, W, ldw, K, e); break;
-    default: launch_gemv_one<false, EPI, NT, DEPTH, PRO, FRAG, 0>(grid, lds, st, A, lda, W, ldw, K, e); break;
+// One launch with the chunks-per-wave specialisation (see gemv_body) when every wave owns cpw chunks -- 4, 8 or, with
+// C16, 16 of them -- and the runtime chunk loop otherwise.
+template <bool HOT, bool C16, int EPI, int NT, int DEPTH, int PRO, int FRAG>
+static void launch_gemv_cpw(int cpw, dim3 grid, size_t lds, hipStream_t st, const bf16_t* A, int lda, const bf16_t* W,
+                            int ldw, int K, const EpiArgs& e) {
+  switch (cpw) {
+    case 4: launch_gemv_one<HOT, EPI, NT, DEPTH, PRO, FRAG, 4>(grid, lds, st, A, lda, W, ldw, K, e); return;
+    case 8: launch_gemv_one<HOT, EPI, NT, DEPTH, PRO, FRAG, 8>(grid, lds, st, A, lda, W, ldw, K, e); return;
+    case 16:
+      if constexpr (C16) {
+        launch_gemv_one<HOT, EPI, NT, DEPTH, PRO, FRAG, 16>(grid, lds, st, A, lda, W, ldw, K, e);
+        return;
+      }
+      [[fallthrough]];
+    default: launch_gemv_one<HOT, EPI, NT, DEPTH, PRO, FRAG, 0>(grid, lds, st, A, lda, W, ldw, K, e);
   }
+}
+
+// bf16 weights, row-major or PG_W_FRAG: NT tiles per workgroup and DEPTH chunks in flight (U = 2: 64-element chunks),
+// the chunks-per-wave specialisation when the K split is exact
+template <int EPI, int NT, int DEPTH, int PRO, bool FRAG>
+static void launch_gemv_tiles(const bf16_t* A, int lda, const bf16_t* W, int ldw, int K, int ksplit, const EpiArgs& e,
+                              hipStream_t st) {
+  const int ntiles = (e.N + 15) / 16, nch = K / 64;
+  const size_t lds = gemv_lds_bytes(PRO, e.M, (nch + ksplit - 1) / ksplit * 64);
+  const int cpw = (nch % ksplit == 0 && (nch / ksplit) % 4 == 0) ? nch / ksplit / 4 : 0;
+  launch_gemv_cpw<false, true, EPI, NT, DEPTH, PRO, FRAG>(cpw, dim3((ntiles + NT - 1) / NT, ksplit), lds, st, A, lda, W,
+                                                          ldw, K, e);
 }
 
 // measured configs (round-1 GEMV sweep): M <= 4: one tile per WG, U=2, 8 chunks in flight;
 // M > 4 and the gate/up pair: two tiles per WG, U=2, 4 chunks in flight.
+// ring depths re-checked on the final round-2 code: two-tile kernels 4 chunks in flight, one-tile 8
 template <int EPI, int PRO, bool FRAG>
 static void launch_gemv_pro(const bf16_t* A, int lda, const bf16_t* W, int ldw, int K, int ksplit, const EpiArgs& e,
                             hipStream_t st) {
-  const int ntiles = (e.N + 15) / 16;
-  const int CH = 64;                                   // U = 2
-  const int per_z = (K / CH + ksplit - 1) / ksplit;
-  size_t lds = 0;
-  if ((PRO != 0 && PRO != 4) || PG_GEMV_XLDS) {
-    lds = (size_t)e.M * (per_z * CH + XPAD) * 2;
-    lds = (lds + 15) & ~(size_t)15;
-    if (PRO == 1) lds += 64 * sizeof(float);
-    if (PRO == 3) lds += 80 * sizeof(float);
+  if constexpr (EPI == PG_EPI_QKV_ROPE) {
+    // batched q|k|v (2560 rows): one tile per workgroup doubles the grid to 160 workgroups
+    if (e.M > 4) return launch_gemv_tiles<EPI, 1, PG_GEMV_D2, PRO, FRAG>(A, lda, W, ldw, K, ksplit, e, st);
   }
-  if constexpr (PG_GEMV_QKV_NT1 && EPI == PG_EPI_QKV_ROPE) {
-    if (e.M > 4) {
-      // batched q|k|v (2560 rows): one tile per workgroup doubles the grid to 160 workgroups
-      launch_gemv_cpw<EPI, 1, PG_GEMV_D2, PRO, FRAG>(dim3(ntiles, ksplit), lds, st, A, lda, W, ldw, K, ksplit, e);
-      return;
-    }
+  if constexpr (EPI == PG_EPI_F32) {
+    // the lm_head at batch 1-4 with two tiles per workgroup (one tile: +5.5 us per token at 6 chunks in flight, +3.5
+    // at 4: profiles/r05_lm_head_nt2_ab.jsonl)
+    if (e.M <= 4 && (e.N + 15) / 16 >= 8192 && ksplit == 1)
+      return launch_gemv_tiles<EPI, 2, PG_GEMV_LM_D, PRO, FRAG>(A, lda, W, ldw, K, 1, e, st);
   }
-  // (four tiles per workgroup at 5..16 rows -- x's share of a workgroup's bytes 1/5 instead of 1/3 -- measured
-  // slower on the pt-448 x16 gate/up and finalised down: 1.408 vs 1.380 ms/step; the epilogues take any even NT)
-  // ring depths re-checked on the final round-2 code: two-tile kernels 4 chunks in flight, one-tile 8
-  if constexpr (PG_GEMV_LM_NT == 2 && EPI == PG_EPI_F32) {
-    if (e.M <= 4 && ntiles >= 8192 && ksplit == 1) {   // (tuning) the lm_head at batch 1-4 with two tiles per workgroup
-      launch_gemv_cpw<EPI, 2, PG_GEMV_LM_D, PRO, FRAG>(dim3((ntiles + 1) / 2, 1), lds, st, A, lda, W, ldw, K, 1, e);
-      return;
-    }
-  }
-  if constexpr (PG_GEMV_FIN_NT == 4 && EPI == PG_EPI_F32_FIN) {
-    if (e.M > 4 && ntiles % 4 == 0) {   // (tuning) the finalised batched down GEMV with four tiles per workgroup
-      launch_gemv_cpw<EPI, 4, PG_GEMV_D2, PRO, FRAG>(dim3(ntiles / 4, ksplit), lds, st, A, lda, W, ldw, K, ksplit, e);
-      return;
-    }
-  }
-  if (EPI == PG_EPI_BF16_GELU_MUL || e.M > 4) {
-    launch_gemv_cpw<EPI, 2, PG_GEMV_D2, PRO, FRAG>(dim3((ntiles + 1) / 2, ksplit), lds, st, A, lda, W, ldw, K, ksplit, e);
-  } else {
-    launch_gemv_cpw<EPI, 1, PG_GEMV_D1, PRO, FRAG>(dim3(ntiles, ksplit), lds, st, A, lda, W, ldw, K, ksplit, e);
-  }
+  // Two tiles per workgroup for the gate/up pair and at 5..16 rows, one tile for the rest.  (Four tiles at 5..16 rows
+  // -- x's share of a workgroup's bytes 1/5 instead of 1/3 -- measured slower on the pt-448 x16 gate/up and finalised
+  // down: 1.408 vs 1.380 ms/step; the epilogues take any even NT.  Round 5: two gate/up pairs per workgroup at batch 1
+  // -- half the workgroups re-reading the row -- measured slower, 1.061 vs 1.059 ms/token at 3 chunks in flight, 1.073
+  // at 2: profiles/r05_gateup_nt4_ab.jsonl)
+  if (EPI == PG_EPI_BF16_GELU_MUL || e.M > 4)
+    launch_gemv_tiles<EPI, 2, PG_GEMV_D2, PRO, FRAG>(A, lda, W, ldw, K, ksplit, e, st);
+  else
+    launch_gemv_tiles<EPI, 1, PG_GEMV_D1, PRO, FRAG>(A, lda, W, ldw, K, ksplit, e, st);
 }
+
 
 template <int EPI, bool FRAG>
 static void launch_gemv(const bf16_t* A, int lda, const bf16_t* W, int ldw, int K, int ksplit, const EpiArgs& e,
@@ -1281,21 +849,11 @@ static void launch_gemv13(const bf16_t* A, int lda, const void* W, int K, int ks
   static_assert(DEPTH % 2 == 0, "whole blocks in flight");
   const int ntiles = e.N / 16;
   const int per_z = K / 64 / ksplit;
-  size_t lds = 0;
-  if (PRO != 0 && PRO != 4) {
-    lds = (size_t)e.M * (per_z * 64 + XPAD) * 2;
-    lds = (lds + 15) & ~(size_t)15;
-    if (PRO == 1) lds += 64 * sizeof(float);
-  }
-  const dim3 grid((ntiles + NT - 1) / NT, ksplit);
-  const bf16_t* w = (const bf16_t*)W;
   // the hot argument header for the forms it gained on; q|k|v and o_proj keep the struct (§A)
   constexpr bool HOT = PRO == 0 || PRO == 4 || EPI == PG_EPI_BF16_GELU_MUL;
-  switch (PG_GEMV_CPW ? per_z / 4 : 0) {
-    case 4: launch_gemv_one<HOT, EPI, NT, DEPTH, PRO, F, 4>(grid, lds, st, A, lda, w, K, K, e); break;
-    case 8: launch_gemv_one<HOT, EPI, NT, DEPTH, PRO, F, 8>(grid, lds, st, A, lda, w, K, K, e); break;
-    default: launch_gemv_one<HOT, EPI, NT, DEPTH, PRO, F, 0>(grid, lds, st, A, lda, w, K, K, e); break;
-  }
+  launch_gemv_cpw<HOT, false, EPI, NT, DEPTH, PRO, F>(per_z / 4, dim3((ntiles + NT - 1) / NT, ksplit),
+                                                      gemv_lds_bytes(PRO, e.M, per_z * 64), st, A, lda,
+                                                      (const bf16_t*)W, K, K, e);
 }
 
 template <int F>

@@ -61,5 +61,4 @@ res["gateup_GBs"] = L[0]["gu_w"].numel() * 2 / res["gateup_us"] / 1e3
 res["down_GBs"] = L[0]["down_w"].numel() * 2 / res["down_s4_us"] / 1e3
 res["lm_head_GBs"] = w.lm_w.numel() * 2 / res["lm_head_us"] / 1e3
 res = {k: round(v, 2) for k, v in res.items()}
-res["knobs"] = {k: os.environ[k] for k in ("PG_GEMV_CPW_OFF", "PG_GEMV_D_NT1", "PG_GEMV_D_NT2") if k in os.environ}
 print(json.dumps(res), flush=True)

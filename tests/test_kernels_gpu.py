@@ -1,5 +1,6 @@
 """Per-kernel numerics on the HIP device: each libpghip entry point against a plain
 PyTorch fp32 reference of the same op on the same (bf16-representable) inputs."""
+import functools
 import math
 
 import numpy as np
@@ -222,6 +223,32 @@ def test_gemm_frag_packed_weights_bit_identical(M, N, K):
         ops.gemm(A, W, a, epi=epi, bias=bb, ksplit=ks)
         ops.gemm(A, Wp, b, epi=epi | ops.W_FRAG, bias=bb, ksplit=ks)
         assert torch.equal(a, b), (epi, ks)
+
+
+@functools.lru_cache(maxsize=None)
+def _lm_head_weights(N, K):
+    """One full-vocabulary weight per K, row-major and fragment-packed, shared by the cases below (read-only)."""
+    from pghip.weights import frag_pack
+    W = rnd(N, K, scale=1 / math.sqrt(K), seed=22)
+    return W, frag_pack(W), torch.randn(N).cuda()
+
+
+@pytest.mark.parametrize("M", [1, 4, 5])
+@pytest.mark.parametrize("K", [64, 1024])
+def test_gemm_frag_two_tile_lm_head_route_bit_identical(M, K):
+    """The two-tile lm_head route of the bf16 GEMV launcher (PG_EPI_F32, M <= 4, N / 16 >= 8192, no K split) -- the
+    production fallback for a matrix without a 13-bit pack, which only a full-vocabulary shape reaches: W_FRAG and
+    row-major outputs are bit-identical there, as in the test above.  K = 64 is one chunk (the runtime chunk loop),
+    K = 1024 four chunks per wave (the straight-line form); M = 5 is the first row count off the route."""
+    from pghip import ops
+    N = 131072
+    A = rnd(M, K, seed=21)
+    W, Wp, bias = _lm_head_weights(N, K)
+    a = torch.empty((1, M, N), dtype=torch.float32, device="cuda")
+    b = torch.empty((1, M, N), dtype=torch.float32, device="cuda")
+    ops.gemm(A, W, a, epi=ops.EPI_F32, bias=bias, ksplit=1)
+    ops.gemm(A, Wp, b, epi=ops.EPI_F32 | ops.W_FRAG, bias=bias, ksplit=1)
+    assert torch.equal(a, b)
 
 
 def test_gemm_vt_and_pos_epilogues():
