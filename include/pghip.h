@@ -243,7 +243,11 @@ int pg_norm_residual(float* resid, const float* partials, int nsplit, int M_part
  * siglip.py:96-136 ; gemma.py:307-339 (repeat_kv :185-196 eliminated).  split_keys > 0: decode
  * split-KV partials, merge with pg_attn_combine; kcap > 0 = readable cache rows (Smax, multiple of 32): each split's
  * first block is loaded before the kv length is read (ABI 2), and (D a multiple of 32) K and V are read from the
- * decode-order copies kd / vd the QKV epilogue writes (PgFusedArgs.kd / vd, ABI 6; null otherwise). */
+ * decode-order copies kd / vd the QKV epilogue writes (PgFusedArgs.kd / vd, ABI 6; null otherwise).
+ * mask (prefill, optional): additive fp32, finite values or -inf; a value whose product with log2 e overflows, such
+ * as FLT_MAX negated (torch.finfo(float32).min), counts as -inf and gives the same bits.  Leading key blocks of a
+ * query row may be wholly masked (left padding, sliding windows), but every row must keep at least one key with a
+ * finite mask value: a row with none has no softmax and its output is NaN.  No NaN and no +inf in a mask. */
 int pg_attention(const void* q, long q_rs, void* o, long o_rs, const void* k, long k_bs, long k_hs,
                  long k_rs, const void* vt, long vt_bs, long vt_hs, long vt_ds, const float* mask,
                  long mask_bs, long mask_rs, int B, int Lq, int Lkv, const int* lkv_dev, int Hq, int Hkv,

@@ -559,10 +559,11 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
     bm = max_xor16(bm);
     bm = max_xor32(bm);
     const float mn = fmaxf(m, bm);
-    const float alpha = exp2f(m - mn);
+    const bool none = mn == -INFINITY;          // every key so far masked (a -inf additive mask): no -inf - -inf
+    const float alpha = none ? 1.f : exp2f(m - mn);
     float rs = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { x[j] = exp2f(x[j] - mn); rs += x[j]; }
+    for (int j = 0; j < 8; ++j) { x[j] = none ? 0.f : exp2f(x[j] - mn); rs += x[j]; }
     rs = sum_xor16(rs);
     rs = sum_xor32(rs);
     l = l * alpha + rs;
@@ -736,10 +737,11 @@ __global__ __launch_bounds__(256) void attn_lds_kernel(AttnArgs a) {
     bm = max_xor16(bm);
     bm = max_xor32(bm);
     const float mn = fmaxf(m, bm);
-    const float alpha = exp2f(m - mn);
+    const bool none = mn == -INFINITY;          // every key so far masked (a -inf additive mask): no -inf - -inf
+    const float alpha = none ? 1.f : exp2f(m - mn);
     float rs = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { x[j] = exp2f(x[j] - mn); rs += x[j]; }
+    for (int j = 0; j < 8; ++j) { x[j] = none ? 0.f : exp2f(x[j] - mn); rs += x[j]; }
     rs = sum_xor16(rs);
     rs = sum_xor32(rs);
     l = l * alpha + rs;
