@@ -268,6 +268,20 @@ int pg_attention_rows(const void* q, long q_rs, void* o, long o_rs, const void* 
                       int D, float scale, int split_keys, int nsplit, float* part_o, float* part_ml,
                       int kcap, const void* kd, const void* vd, hipStream_t stream);
 
+/* (added under ABI 13; the version stays 13)  Prefix-LM prefill attention: pg_attention_rows in prefill mode plus
+ * prefix_rows int32 [B] in device memory.  With len_b = clamp(lkv_rows[b], 1, Lkv) and prefix_b = clamp(prefix_rows[b],
+ * 1, len_b), row b's query at position p (0-based) attends key j iff j < min(len_b, max(prefix_b, p + 1)): the first
+ * prefix_b positions (image + prompt) attend one another fully, the positions after them (the answer) causally, so a
+ * given answer is scored in one prefill pass.  prefix_b == len_b gives pg_attention_rows' bits, prefix_b == 1 plain
+ * causal attention.  Every kernel form takes the rule (key splits and an additive mask on top included).  Prefill
+ * only: split_keys must be 0 (kcap, kd, vd are ignored).  Null q / o / k / vt / lkv_rows / prefix_rows, empty shapes
+ * and misaligned pointers return hipErrorInvalidValue before anything is launched. */
+int pg_attention_prefix(const void* q, long q_rs, void* o, long o_rs, const void* k, long k_bs, long k_hs,
+                        long k_rs, const void* vt, long vt_bs, long vt_hs, long vt_ds, const float* mask,
+                        long mask_bs, long mask_rs, int B, int Lq, int Lkv, const int* lkv_rows,
+                        const int* prefix_rows, int Hq, int Hkv, int D, float scale, int split_keys, int nsplit,
+                        float* part_o, float* part_ml, int kcap, const void* kd, const void* vd, hipStream_t stream);
+
 /* The attention weights the reference's modules return, out fp32 [B][Hq][Lq][Lkv] with pg_attention's q / k / mask
  * addressing: probs = 1 softmax(q . k^T * scale + mask) (gemma.py:358), probs = 0 the scaled scores + mask before the
  * softmax (siglip.py:157 returns those).  The module API's opt-in (the flash kernels never form this matrix; at
@@ -329,6 +343,15 @@ int pg_argmax_embed(const float* logits, long ld, int B, int V, void* workspace,
                     int64_t* hist, int hist_rows, int* step, int* pos, int* kv_len, const void* embed, int V_embed,
                     const float* feat, int n_feat, int H, long image_id, long pad_id, float img_scale,
                     float normalizer, float* res, hipStream_t stream);
+
+/* (added under ABI 13)  Log-probability of a given token per row, for scoring an answer: logprob[r] =
+ * logits[r][targets[r]] - logsumexp(logits[r][0:V]) in fp32, and top1[r] (nullable) the row's argmax, lowest index on
+ * ties as pg_argmax.  logits fp32, row stride ld floats (>= V when R > 1; any alignment of 4 bytes, 16-B loads where
+ * the rows allow them), read once; a row is split over 64 workgroups and merged through workspace (>= R * (64 * 12 + 4)
+ * bytes, 16-B aligned).  -inf entries are legal and add 0; a target outside [0, V) gives -inf (nothing is read for
+ * it); a row of nothing but -inf gives -inf; the row max is subtracted before any exp.  R <= 65535. */
+int pg_token_logprob(const float* logits, long ld, int R, int V, const int64_t* targets, float* logprob,
+                     int64_t* top1, void* workspace, hipStream_t stream);
 
 /* vocabulary-parallel greedy for tensor parallelism: local (max, first global index) pairs [B][2] of a
  * vocab shard starting at vocab_offset; after an all-gather, pg_argmax_merge takes the global winner

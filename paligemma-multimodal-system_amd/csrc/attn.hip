@@ -454,7 +454,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_decode_fused_kernel(AttnArgs 
 #endif
 }
 
-template <int DP, int DT>
+// PFX (pg_attention_prefix): the wave walks the keys its last position sees and each query masks at its own count.
+template <int DP, int DT, bool PFX = false>
 __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
   constexpr int KS = DP / 32;  // QK^T k-steps
   const int lane = threadIdx.x & 63;
@@ -488,6 +489,12 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
   const bool rvalid = r < R;
   const int pos = rvalid ? r / a.G : 0;
   const int hq = kvh * a.G + (rvalid ? r % a.G : 0);
+  int vis = Lkv;                                   // keys this lane's query attends
+  if constexpr (PFX) {
+    const int pfx = attn_prefix_keys(a, b, Lkv);
+    kend = attn_visible(Lkv, pfx, min(__builtin_amdgcn_readfirstlane(r0) + 15, R - 1) / a.G);
+    vis = attn_visible(Lkv, pfx, pos);
+  }
 
   bf16x8 qf[KS];
   {
@@ -550,8 +557,8 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
         v0 += mrow[min(k0, kend - 1)] * LOG2E;
         v1 += mrow[min(k1, kend - 1)] * LOG2E;
       }
-      x[j] = k0 < kend ? v0 : -INFINITY;
-      x[4 + j] = k1 < kend ? v1 : -INFINITY;
+      x[j] = k0 < (PFX ? vis : kend) ? v0 : -INFINITY;
+      x[4 + j] = k1 < (PFX ? vis : kend) ? v1 : -INFINITY;
     }
     float bm = x[0];
 #pragma unroll
@@ -615,7 +622,8 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
 // so K/V leave L2 once per 64 rows instead of once per 16 (pt-448 x16: 1 MB of K/V per 16 rows).
 // Rows are padded by 16 B so the MFMA fragment reads are bank-conflict free; K rows past Lkv are
 // clamped (their scores are masked) and V^T keys past Lkv are zeroed at staging.
-template <int DP, int DT>
+// PFX (pg_attention_prefix): the workgroup walks the blocks its last position sees; each query masks at its own count.
+template <int DP, int DT, bool PFX = false>
 __global__ __launch_bounds__(256) void attn_lds_kernel(AttnArgs a) {
   constexpr int KS = DP / 32;
   constexpr int KROW = DP * 2 + 16;          // bytes per staged K row
@@ -638,6 +646,12 @@ __global__ __launch_bounds__(256) void attn_lds_kernel(AttnArgs a) {
   const bool rvalid = r < R;                 // invalid rows still stage and hit every barrier
   const int pos = rvalid ? r / a.G : 0;
   const int hq = kvh * a.G + (rvalid ? r % a.G : 0);
+  int vis = Lkv, kwalk = Lkv;                // keys this lane's query attends / the workgroup walks
+  if constexpr (PFX) {
+    const int pfx = attn_prefix_keys(a, b, Lkv);
+    kwalk = attn_visible(Lkv, pfx, min((int)blockIdx.x * 64 + 63, R - 1) / a.G);
+    vis = attn_visible(Lkv, pfx, pos);
+  }
 
   bf16x8 qf[KS];
   {
@@ -700,7 +714,7 @@ __global__ __launch_bounds__(256) void attn_lds_kernel(AttnArgs a) {
   for (int tt = 0; tt < DT; ++tt) o[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;
   const float LOG2E = 1.4426950408889634f;
-  const int nblk = (Lkv + 31) / 32;
+  const int nblk = (kwalk + 31) / 32;
 
   gload(0);
   lstore(0);
@@ -728,8 +742,8 @@ __global__ __launch_bounds__(256) void attn_lds_kernel(AttnArgs a) {
         v0 += mrow[min(k0, Lkv - 1)] * LOG2E;
         v1 += mrow[min(k1, Lkv - 1)] * LOG2E;
       }
-      x[j] = k0 < Lkv ? v0 : -INFINITY;
-      x[4 + j] = k1 < Lkv ? v1 : -INFINITY;
+      x[j] = k0 < vis ? v0 : -INFINITY;
+      x[4 + j] = k1 < vis ? v1 : -INFINITY;
     }
     float bm = x[0];
 #pragma unroll
@@ -798,7 +812,14 @@ __global__ __launch_bounds__(256) void attn_lds_kernel(AttnArgs a) {
 // skipped when no row's max moved), and 2 x DT PV MFMAs.  Keys past Lkv: K rows clamped, scores -inf,
 // V^T chunks clamped to the last readable 8-key chunk (rup8(Lkv) keys must be readable per V^T row);
 // K dims past D (D < DP) are never read from memory.
-template <int DP, int DT, int WAVES, int RPW, int KB = 64, int NST = 2>
+// PFX (pg_attention_prefix; every other instance compiles to what it was): batch row b's first prefix_b positions
+// attend one another, the later ones causally (attn_visible).  With stacked row r = (pos, head) position-major, a
+// workgroup's rows span positions [p_lo, p_hi]: it walks the key blocks up to what p_hi sees, a wave takes the unmasked
+// path for the blocks below what its own first position sees, and only the blocks past that compare per lane.  A row
+// may then meet a block -- in a key split, a whole split -- with no visible key: its running max stays -inf and the
+// exponents are taken against 0 instead (exp2(-inf - -inf) is NaN), which leaves m, l and O as they were; a split
+// with none writes the neutral partial (m = -inf, l = 0, O = 0) that the merge skips.
+template <int DP, int DT, int WAVES, int RPW, int KB = 64, int NST = 2, bool PFX = false>
 __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
   static_assert(KB == 64 || KB == 32, "64- or 32-key blocks");
   constexpr int KS = DP / 32;
@@ -844,6 +865,19 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
       qf[i][s] = __builtin_bit_cast(bf16x8, ld16_sel(qp + (d0 < D ? d0 : 0), rvalid[i] && d0 < D));
     }
   }
+  // keys the workgroup walks (kwalk), keys every row of this wave sees (kfull: blocks below it are not masked) and
+  // keys each lane's queries see (vis); all three are the row's length unless PFX
+  int kwalk = Lkv, kfull = Lkv, vis[RPW];
+#pragma unroll
+  for (int i = 0; i < RPW; ++i) vis[i] = Lkv;
+  if constexpr (PFX) {
+    const int pfx = attn_prefix_keys(a, b, Lkv);
+    const int rows = WAVES * RPW * 16;
+    kwalk = attn_visible(Lkv, pfx, min(rt * rows + rows - 1, R - 1) / a.G);
+    kfull = attn_visible(Lkv, pfx, min((rt * WAVES + wave) * RPW * 16, R - 1) / a.G);
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) vis[i] = attn_visible(Lkv, pfx, pos[i]);
+  }
   const bf16_t* kbase = a.k + (long)b * a.k_bs + (long)kvh * a.k_hs;
   const bf16_t* vbase = a.vt + (long)b * a.vt_bs + (long)kvh * a.vt_hs;
   const int vkey_max = ((Lkv + 7) & ~7) - 8;       // last readable 8-key chunk of a V^T row
@@ -885,7 +919,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
 #pragma unroll
     for (int tt = 0; tt < DT; ++tt) o[i][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  const int nblk_all = (Lkv + KB - 1) / KB;
+  const int nblk_all = (kwalk + KB - 1) / KB;
   const int per = (nblk_all + nks - 1) / nks;
   const int kb0 = ks * per * KB;                   // first key of this split
   const int nblk = max(0, min(nblk_all - ks * per, per));
@@ -936,7 +970,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
       for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
         for (int j = 0; j < 4; ++j) x[4 * kt + j] = sc[i][kt][j];
-      if (kb + KB > Lkv) {
+      if (kb + KB > kfull) {
         // (the empty volatile asm keeps this a branch: if-converted, the ~50 compares and selects of the key mask ran
         // on every block, a third of the softmax's VALU)
         if constexpr (PG_FA_MASK_BRANCH) asm volatile("");
@@ -944,7 +978,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
         for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            if (kb + 32 * (kt >> 1) + 8 * g + 4 * (kt & 1) + j >= Lkv) x[4 * kt + j] = -INFINITY;
+            if (kb + 32 * (kt >> 1) + 8 * g + 4 * (kt & 1) + j >= vis[i]) x[4 * kt + j] = -INFINITY;
       }
       float bm = x[0];
 #pragma unroll
@@ -952,6 +986,8 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
       bm = max_xor16(bm);
       bm = max_xor32(bm);
       float mn = fmaxf(m[i], bm * a.scale_log2);         // = the max of the scaled scores (scaling is monotonic)
+      // (PFX: no key visible to this row yet -- the exponents against 0, so alpha = 0 and every P = 0, not NaN)
+      auto msub = [](float v) { return PFX && v == -INFINITY ? 0.f : v; };
       float alpha;
       if constexpr (LAZY > 0) {
         // lazy rescale: the running max moves (and O, l are rescaled) only when some row of the wave gained more than
@@ -961,16 +997,16 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
         alpha = 1.0f;
         if (__builtin_amdgcn_ballot_w64(mn > m[i] + (float)LAZY)) {
           asm volatile("");
-          alpha = __builtin_amdgcn_exp2f(m[i] - mn);
+          alpha = __builtin_amdgcn_exp2f(m[i] - msub(mn));
 #pragma unroll
           for (int tt = 0; tt < DT; ++tt) o[i][tt] *= alpha;
           m[i] = mn;
         }
         mn = m[i];
       } else {
-        alpha = __builtin_amdgcn_exp2f(m[i] - mn);
+        alpha = __builtin_amdgcn_exp2f(m[i] - msub(mn));
       }
-      const f32x2 s2 = {a.scale_log2, a.scale_log2}, n2 = {-mn, -mn};
+      const f32x2 s2 = {a.scale_log2, a.scale_log2}, n2 = {-msub(mn), -msub(mn)};
       f32x2 rs2 = {0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < 4 * NKT; j += 2) {
@@ -1190,54 +1226,61 @@ struct FaWide {
   static constexpr int NST = N > PG_FA_NST8 ? PG_FA_NST8 : N;
 };
 
-template <int DP, int DT>
+// (PFX: the prefix-LM instances of pg_attention_prefix, the same forms)
+template <int DP, int DT, bool PFX>
 static void launch_fa(int waves, int rpw, bool deep, dim3 grid, hipStream_t stream, const AttnArgs& a) {
   if (deep && waves == 4 && rpw == 1) {
-    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 4, 1, FaDeep<DP, DT>::KB, FaDeep<DP, DT>::NST>), grid, dim3(256), 0,
+    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 4, 1, FaDeep<DP, DT>::KB, FaDeep<DP, DT>::NST, PFX>), grid, dim3(256), 0,
                        stream, a);
     return;
   }
   if constexpr (PG_FA_RPW == 2) {
     if constexpr (DP <= 96) {       // (DP 128 at 8 x 32 rows needs > 256 registers: 1 wave / SIMD)
       if (waves == 8 && rpw == 2) {
-        hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 8, 2>), grid, dim3(512), 0, stream, a);
+        hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 8, 2, 64, 2, PFX>), grid, dim3(512), 0, stream, a);
         return;
       }
     }
     if (waves == 4 && rpw == 2) {
-      hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 4, 2>), grid, dim3(256), 0, stream, a);
+      hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 4, 2, 64, 2, PFX>), grid, dim3(256), 0, stream, a);
       return;
     }
   }
   if constexpr (DP == 256) {
     if (waves == 8 && rpw == 2) {
-      hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 8, 2, 32, PG_FA_W8R2_NST>), grid, dim3(512), 0, stream, a);
+      hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 8, 2, 32, PG_FA_W8R2_NST, PFX>), grid, dim3(512), 0, stream, a);
       return;
     }
     if (waves == 12) {
-      hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 12, 1, FaWide<DP, DT>::KB, FaWide<DP, DT>::NST>), grid, dim3(768), 0,
-                         stream, a);
+      hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 12, 1, FaWide<DP, DT>::KB, FaWide<DP, DT>::NST, PFX>), grid, dim3(768),
+                         0, stream, a);
       return;
     }
   }
   if (waves == 8)
-    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 8, 1, FaWide<DP, DT>::KB, FaWide<DP, DT>::NST>), grid, dim3(512), 0,
+    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 8, 1, FaWide<DP, DT>::KB, FaWide<DP, DT>::NST, PFX>), grid, dim3(512), 0,
                        stream, a);
   else if (waves == 2)
-    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 2, 1>), grid, dim3(128), 0, stream, a);
+    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 2, 1, 64, 2, PFX>), grid, dim3(128), 0, stream, a);
   else if (waves == 1)
-    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 1, 1>), grid, dim3(64), 0, stream, a);
+    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 1, 1, 64, 2, PFX>), grid, dim3(64), 0, stream, a);
   else
-    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 4, 1>), grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 4, 1, 64, 2, PFX>), grid, dim3(256), 0, stream, a);
 }
 
 
 #define ATTN_DISPATCH(DP_, DT_)                                                             \
   if (DP == DP_ && DT == DT_) {                                                              \
-    if (fa_waves)                                                                            \
-      launch_fa<DP_, DT_>(fa_waves, fa_rpw, fa_deep, grid, stream, a);                       \
+    if (fa_waves && a.prefix_rows)                                                           \
+      launch_fa<DP_, DT_, true>(fa_waves, fa_rpw, fa_deep, grid, stream, a);                 \
+    else if (fa_waves)                                                                       \
+      launch_fa<DP_, DT_, false>(fa_waves, fa_rpw, fa_deep, grid, stream, a);                \
+    else if (use_lds && a.prefix_rows)                                                       \
+      hipLaunchKernelGGL((attn_lds_kernel<DP_, DT_, true>), grid, dim3(256), 0, stream, a);  \
     else if (use_lds)                                                                        \
       hipLaunchKernelGGL((attn_lds_kernel<DP_, DT_>), grid, dim3(256), 0, stream, a);        \
+    else if (a.prefix_rows)                                                                  \
+      hipLaunchKernelGGL((attn_kernel<DP_, DT_, true>), grid, dim3(64), 0, stream, a);       \
     else if (split_keys > 0 && PG_ATTN_SPLIT_WAVES == 1 && D == DP_ && kcap >= 32 && PG_ATTN_WG && DP_ == 256 && \
              (split_keys == 64 || split_keys % 128 == 0)) {                                  \
       if (split_keys == 64)                                                                  \
@@ -1264,11 +1307,13 @@ static void launch_fa(int waves, int rpw, bool deep, dim3 grid, hipStream_t stre
 // loads before the kv length arrives from lkv_dev; 0 = rows clamped to the kv length.  Decode with kcap > 0 and
 // D a multiple of 32 reads K and V only from the decode-order copies kd / vd ([B][Hkv][kcap][D], ABI 6).
 // lkv_rows (pg_attention_rows; null for pg_attention): int32 [B] per-row key counts, see the entry point below.
+// prefix_rows (pg_attention_prefix, with lkv_rows, prefill only; null otherwise): int32 [B] per-row prefix lengths.
 static int attention_impl(const void* q, long q_rs, void* o, long o_rs, const void* k, long k_bs, long k_hs,
                           long k_rs, const void* vt, long vt_bs, long vt_hs, long vt_ds, const float* mask,
                           long mask_bs, long mask_rs, int B, int Lq, int Lkv, const int* lkv_dev, int Hq, int Hkv,
                           int D, float scale, int split_keys, int nsplit, float* part_o, float* part_ml,
-                          int kcap, const void* kd, const void* vd, const int* lkv_rows, hipStream_t stream) {
+                          int kcap, const void* kd, const void* vd, const int* lkv_rows, const int* prefix_rows,
+                          hipStream_t stream) {
   PG_REQUIRE(B > 0 && Lq > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && D > 0 && D % 8 == 0 && D <= 256);
   // (split mode writes partials only: o is read by nobody, the merge is pg_attn_combine's or the o_proj prologue's)
   PG_REQUIRE(kcap >= 0 && kcap % 32 == 0 && q && (split_keys == 0 ? o != nullptr : (part_o && part_ml)));
@@ -1288,6 +1333,7 @@ static int attention_impl(const void* q, long q_rs, void* o, long o_rs, const vo
     a.lkv_stride = 1;
     a.lkv_max = split_keys > 0 ? 0x7fffffff : Lkv;
     if (split_keys == 0) a.Lkv = 0;
+    a.prefix_rows = prefix_rows;                   // picks the PFX instance of whichever prefill form is taken
   }
   dim3 grid;
   // prefill with >= 1024 one-wave workgroups: the LDS-staged kernel (64 rows per workgroup share K/V);
@@ -1303,6 +1349,8 @@ static int attention_impl(const void* q, long q_rs, void* o, long o_rs, const vo
   const bool off32 = (unsigned long)(Lkv + 64) * (unsigned long)k_rs * 2ul < (1ul << 32) &&
                      (unsigned long)D * (unsigned long)vt_ds * 2ul < (1ul << 32);
   if (split_keys == 0 && mask == nullptr && aligned && off32 && lkv_dev == nullptr && PG_ATTN_FA) {
+    // (tests/test_score_gpu.py fa_form restates the wgs / rounds rules below at the default knobs, to know a shape's
+    // workgroup rows and key block: a change of rule or default here is a change there)
     auto wgs = [&](int rows) { return (long)((Lq * G + rows - 1) / rows) * Hkv * B; };
     // two 16-row groups per wave (half the LDS fragment reads per flop) when the grid still fills the chip:
     // 8 waves x 32 rows for head_dim <= 96, else 4 waves x 32 rows (their accumulators need 1 wave / SIMD)
@@ -1382,7 +1430,7 @@ extern "C" int pg_attention(const void* q, long q_rs, void* o, long o_rs, const 
                             int kcap, const void* kd, const void* vd, hipStream_t stream) {
   return attention_impl(q, q_rs, o, o_rs, k, k_bs, k_hs, k_rs, vt, vt_bs, vt_hs, vt_ds, mask, mask_bs, mask_rs, B, Lq,
                         Lkv, lkv_dev, Hq, Hkv, D, scale, split_keys, nsplit, part_o, part_ml, kcap, kd, vd, nullptr,
-                        stream);
+                        nullptr, stream);
 }
 
 // pg_attention with one kv length per batch row, lkv_rows int32 [B] in device memory (prompts of different lengths in
@@ -1402,7 +1450,31 @@ extern "C" int pg_attention_rows(const void* q, long q_rs, void* o, long o_rs, c
   PG_REQUIRE(lkv_rows != nullptr && B > 0 && Lkv >= (split_keys > 0 ? 0 : 1));
   return attention_impl(q, q_rs, o, o_rs, k, k_bs, k_hs, k_rs, vt, vt_bs, vt_hs, vt_ds, mask, mask_bs, mask_rs, B, Lq,
                         Lkv, nullptr, Hq, Hkv, D, scale, split_keys, nsplit, part_o, part_ml, kcap, kd, vd, lkv_rows,
-                        stream);
+                        nullptr, stream);
+}
+
+// Prefix-LM prefill attention: pg_attention_rows in prefill mode plus prefix_rows int32 [B] (device memory).  For batch
+// row b, len_b = clamp(lkv_rows[b], 1, Lkv) and prefix_b = clamp(prefix_rows[b], 1, len_b); the query at position p
+// attends key j iff j < min(len_b, max(prefix_b, p + 1)): image and prompt positions attend one another fully, answer
+// positions causally (a whole answer scored in one prefill pass).  prefix_b == len_b is pg_attention_rows bit for bit,
+// prefix_b == 1 plain causal attention.  Every form attention_impl picks takes the rule (the PFX instances: the flash
+// forms with and without key splits, and under an additive mask the LDS-staged and one-wave kernels); the same
+// conditions on K / V^T as pg_attention_rows.  Prefill only: split_keys must be 0.
+extern "C" int pg_attention_prefix(const void* q, long q_rs, void* o, long o_rs, const void* k, long k_bs, long k_hs,
+                                   long k_rs, const void* vt, long vt_bs, long vt_hs, long vt_ds, const float* mask,
+                                   long mask_bs, long mask_rs, int B, int Lq, int Lkv, const int* lkv_rows,
+                                   const int* prefix_rows, int Hq, int Hkv, int D, float scale, int split_keys,
+                                   int nsplit, float* part_o, float* part_ml, int kcap, const void* kd, const void* vd,
+                                   hipStream_t stream) {
+  PG_REQUIRE(split_keys == 0 && lkv_rows != nullptr && prefix_rows != nullptr && q && o && k && vt);
+  PG_REQUIRE(B > 0 && Lq > 0 && Lkv >= 1 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && D > 0 && nsplit >= 0);
+  PG_REQUIRE(((uintptr_t)lkv_rows & 3) == 0 && ((uintptr_t)prefix_rows & 3) == 0 && ((uintptr_t)q & 15) == 0 &&
+             ((uintptr_t)o & 7) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)vt & 15) == 0 &&
+             (mask == nullptr || ((uintptr_t)mask & 3) == 0));
+  PG_REQUIRE(nsplit <= 1 || (part_o && part_ml && ((uintptr_t)part_o & 15) == 0 && ((uintptr_t)part_ml & 7) == 0));
+  return attention_impl(q, q_rs, o, o_rs, k, k_bs, k_hs, k_rs, vt, vt_bs, vt_hs, vt_ds, mask, mask_bs, mask_rs, B, Lq,
+                        Lkv, nullptr, Hq, Hkv, D, scale, 0, nsplit, part_o, part_ml, kcap, kd, vd, lkv_rows,
+                        prefix_rows, stream);
 }
 
 extern "C" int pg_attn_combine(const float* part_o, const float* part_ml, int B, int Hq, int Hkv, int D, int nsplit,

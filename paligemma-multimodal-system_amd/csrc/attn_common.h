@@ -36,6 +36,8 @@ struct AttnArgs {
   int lkv_stride;          // 0: lkv_dev is one word shared by the batch; 1: int32 [B], row b reads lkv_dev[b]
                            // (pg_attention_rows / pg_attn_decode_rows: prompts of different lengths in one batch)
   int lkv_max;             // prefill with lkv_stride 1: row b attends min(max(lkv_dev[b], 1), lkv_max) keys
+  const int* prefix_rows;  // prefill, pg_attention_prefix (the PFX kernel instances; null otherwise): int32 [B], row b's
+                           // first prefix_rows[b] positions attend one another, the later ones causally (attn_visible)
 };
 
 // the kv-length word of batch row b (a zero word when there is none: no select on the loaded value)
@@ -48,6 +50,12 @@ static __device__ __forceinline__ int attn_prefill_keys(const AttnArgs& a, int b
   const int n = __builtin_amdgcn_readfirstlane(a.lkv_dev[b * a.lkv_stride]) + a.Lkv;
   return a.lkv_stride ? min(max(n, 1), a.lkv_max) : n;
 }
+// pg_attention_prefix: batch row b's prefix length, clamped to [1, len] (wave-uniform), and the keys the query at
+// position p attends: all of the prefix, else its own position and everything before it, never past the row's length
+static __device__ __forceinline__ int attn_prefix_keys(const AttnArgs& a, int b, int len) {
+  return min(max(__builtin_amdgcn_readfirstlane(a.prefix_rows[b]), 1), len);
+}
+static __device__ __forceinline__ int attn_visible(int len, int prefix, int p) { return min(len, max(prefix, p + 1)); }
 
 // Decode-order copies of the static KV cache (ABI 6).  The QKV epilogue writes every appended k / v twice: to the
 // canonical K [.][Smax][D] / V^T [.][D][Smax] (prefill attention, the reference KVCache views) and to these copies,

@@ -445,6 +445,128 @@ extern "C" int pg_argmax_embed(const float* logits, long ld, int B, int V, void*
   return 0;
 }
 
+// ---------------------------------------------------------------- token log-probabilities (two passes)
+// logprob[r] = x[r][t_r] - logsumexp(x[r][0:V]) and top1[r] = argmax (first index on ties), for scoring a given
+// answer.  As pg_argmax, a row is cut into TL_CHUNKS chunks, one workgroup each (32 rows of 257 216 are 2048
+// workgroups, not 32): every thread keeps a running (max, sum of exp(x - max), best index) over its part of the chunk
+// -- the logits are read once, the thread that loads column t_r keeps it -- and the chunk's merged triple goes to the
+// workspace; the final pass merges a row's TL_CHUNKS triples in one wave.  -inf entries add 0; a row with nothing
+// above -inf gives -inf, not NaN; the max is subtracted, so +-1e4 does not overflow.
+#define TL_CHUNKS 64
+// (m, s) <- the online-softmax merge of (m, s) and (m2, s2): s sums exp(x - m); an empty side has m = -inf, s = 0
+__device__ __forceinline__ void tl_merge(float& m, float& s, float m2, float s2) {
+  const float M = fmaxf(m, m2);
+  s = (m == -INFINITY ? 0.f : s * __expf(m - M)) + (m2 == -INFINITY ? 0.f : s2 * __expf(m2 - M));
+  m = M;
+}
+struct TlPartArgs {
+  const float* x;
+  long ld;
+  int V;
+  const int64_t* targets;
+  float* pm;      // [R][TL_CHUNKS] chunk max
+  float* ps;      // [R][TL_CHUNKS] chunk sum of exp(x - max)
+  int* pi;        // [R][TL_CHUNKS] chunk argmax
+  float* pt;      // [R] the target's logit (written only when the target is inside [0, V))
+};
+template <bool VEC>
+__global__ __launch_bounds__(256) void token_logprob_partial_kernel(TlPartArgs a) {
+  __shared__ float sv[4], sm[4], ss[4];
+  __shared__ int si[4];
+  const int r = blockIdx.y, ch = blockIdx.x;
+  const int per = ((a.V + TL_CHUNKS - 1) / TL_CHUNKS + 3) & ~3;
+  const int s0 = ch * per, e = min(a.V, s0 + per);
+  const float* row = a.x + (long)r * a.ld;
+  const int64_t t64 = a.targets[r];
+  const int tgt = t64 >= 0 && t64 < a.V ? (int)t64 : -1;
+  float bv = -INFINITY, m = -INFINITY, s = 0.f;
+  int bi = AM_NONE;
+  for (int i = s0 + threadIdx.x * 4; i < e; i += 1024) {
+    float v[4];
+    if (VEC && i + 3 < e) {
+      const f32x4 q = *(const f32x4*)(row + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = q[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = i + j < e ? row[i + j] : -INFINITY;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (i + j < e) am_better(bv, bi, v[j], i + j);
+    if (tgt >= i && tgt < i + 4 && tgt < e) a.pt[r] = v[tgt - i];
+    const float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+    if (mx > m) {                                  // (m = -inf: s = 0 and exp(-inf) = 0)
+      s *= __expf(m - mx);
+      m = mx;
+    }
+    if (m != -INFINITY) s += (__expf(v[0] - m) + __expf(v[1] - m)) + (__expf(v[2] - m) + __expf(v[3] - m));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) tl_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+  if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = m; ss[threadIdx.x >> 6] = s; }
+  am_block(bv, bi, sv, si);                        // (its barrier publishes sm / ss too)
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) tl_merge(m, s, sm[w], ss[w]);
+    a.pm[r * TL_CHUNKS + ch] = m;
+    a.ps[r * TL_CHUNKS + ch] = s;
+    a.pi[r * TL_CHUNKS + ch] = bi;
+  }
+}
+
+// one wave per row: lane ch holds chunk ch's triple
+__global__ __launch_bounds__(1024) void token_logprob_final_kernel(const float* __restrict__ pm,
+                                                                   const float* __restrict__ ps,
+                                                                   const int* __restrict__ pi,
+                                                                   const float* __restrict__ pt,
+                                                                   const int64_t* __restrict__ targets, int R, int V,
+                                                                   float* __restrict__ logprob,
+                                                                   int64_t* __restrict__ top1) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  for (int r = blockIdx.x * nw + wave; r < R; r += gridDim.x * nw) {
+    const float m = pm[r * TL_CHUNKS + lane];
+    float bv = m;
+    int bi = pi[r * TL_CHUNKS + lane];
+    const float M = wave_max(m);
+    const float S = wave_sum(m == -INFINITY ? 0.f : ps[r * TL_CHUNKS + lane] * __expf(m - M));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      float ov = __shfl_xor(bv, o, 64);
+      int oi = __shfl_xor(bi, o, 64);
+      am_better(bv, bi, ov, oi);
+    }
+    if (lane == 0) {
+      const int64_t t = targets[r];
+      // (x_t - M first: exact for a target near the max, where x_t - (M + log S) would round at the logits' scale)
+      logprob[r] = (t >= 0 && t < V && M != -INFINITY) ? (pt[r] - M) - __logf(S) : -INFINITY;
+      if (top1) top1[r] = am_id(bi);
+    }
+  }
+}
+
+// workspace: >= R * (TL_CHUNKS * 12 + 4) bytes, 16-B aligned.  ld: row stride in floats (>= V when R > 1).
+extern "C" int pg_token_logprob(const float* logits, long ld, int R, int V, const int64_t* targets, float* logprob,
+                                int64_t* top1, void* workspace, hipStream_t stream) {
+  PG_REQUIRE(logits && targets && logprob && workspace && R > 0 && V > 0 && (R == 1 || ld >= V));
+  PG_REQUIRE(R <= 65535 && ((uintptr_t)logits & 3) == 0 && ((uintptr_t)targets & 7) == 0 &&
+             ((uintptr_t)logprob & 3) == 0 && ((uintptr_t)top1 & 7) == 0 && ((uintptr_t)workspace & 15) == 0);
+  float* pm = (float*)workspace;
+  float* ps = pm + (long)R * TL_CHUNKS;
+  int* pi = (int*)(ps + (long)R * TL_CHUNKS);
+  float* pt = (float*)(pi + (long)R * TL_CHUNKS);
+  const TlPartArgs pa{logits, ld, V, targets, pm, ps, pi, pt};
+  // 16-B loads where every chunk start is 16-B aligned (chunks are multiples of 4 columns)
+  if (((uintptr_t)logits & 15) == 0 && ld % 4 == 0)
+    hipLaunchKernelGGL(token_logprob_partial_kernel<true>, dim3(TL_CHUNKS, R), dim3(256), 0, stream, pa);
+  else
+    hipLaunchKernelGGL(token_logprob_partial_kernel<false>, dim3(TL_CHUNKS, R), dim3(256), 0, stream, pa);
+  const int nw = am_waves(R);
+  hipLaunchKernelGGL(token_logprob_final_kernel, dim3((R + nw - 1) / nw > 64 ? 64 : (R + nw - 1) / nw), dim3(64 * nw), 0,
+                     stream, pm, ps, pi, pt, targets, R, V, logprob, top1);
+  PG_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---------------------------------------------------------------- top-p sampling (one workgroup per row)
 // p_i = softmax(logits / T).  Included set = tokens whose probability mass strictly ranked before them is
 // <= top_p, i.e. {e_i >= t0} with t0 the smallest value whose strictly-greater mass F(t0) <= top_p * Z.

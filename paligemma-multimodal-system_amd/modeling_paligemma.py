@@ -182,6 +182,17 @@ class PaliGemmaForConditionalGeneration(nn.Module):
         return {"logits": logits, "kv_cache": cache}
 
     @torch.no_grad()
+    def score(self, input_ids, pixel_values, attention_mask, token_type_ids, return_logits: bool = False) -> dict:
+        """How likely given answers are: row b of input_ids is its prompt row followed by an answer and padding
+        (PaliGemmaProcessor.batch(..., suffixes=...)), token_type_ids 1 over the answer.  One prefix-LM prefill (the
+        prompt attends itself fully, the answer causally) instead of one decode step per answer token; returns the
+        engine's dict: "logprobs" fp32 [B][S_max] (log p of each answer token given everything before it, 0 past the
+        answer), "top1" int64 [B][S_max] (the model's own choice there), "suffix_lens", and "logits" on request
+        (PaliGemmaEngine.score)."""
+        eng = self.engine(input_ids.device)
+        return eng.score(input_ids, pixel_values, attention_mask, token_type_ids, return_logits=return_logits)
+
+    @torch.no_grad()
     def generate(self, input_ids, pixel_values, attention_mask=None, max_new_tokens: int = 100,
                  do_sample: bool = False, temperature: float = 0.8, top_p: float = 0.9, uniforms=None,
                  stop_token: Optional[int] = 1):

@@ -44,6 +44,8 @@ SIGNATURES = {
                      i32, i32, i32, vp, i32, i32, i32, f32, i32, i32, vp, vp, i32, vp, vp, vp],
     "pg_attention_rows": [vp, i64, vp, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64,
                           i32, i32, i32, vp, i32, i32, i32, f32, i32, i32, vp, vp, i32, vp, vp, vp],
+    "pg_attention_prefix": [vp, i64, vp, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64,
+                            i32, i32, i32, vp, vp, i32, i32, i32, f32, i32, i32, vp, vp, i32, vp, vp, vp],
     "pg_attn_combine": [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp],
     "pg_attn_probs": [vp, i64, vp, i64, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp],
     "pg_attn_decode": [vp, i64, vp, i64, vp, vp, i32, i32, vp, i32, i32, i32, f32, i32, i32, i32, i32, vp, vp, vp,
@@ -55,6 +57,7 @@ SIGNATURES = {
     "pg_image_rank": [vp, i32, i64, vp, vp],
     "pg_embed_merge": [vp, vp, i32, vp, i32, vp, i32, i32, i64, i64, f32, f32, vp, vp],
     "pg_argmax": [vp, i64, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp],
+    "pg_token_logprob": [vp, i64, i32, i32, vp, vp, vp, vp, vp],
     "pg_argmax_embed": [vp, i64, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, i64, i64, f32, f32, vp,
                         vp],
     "pg_argmax_pairs": [vp, i64, i32, i32, i32, vp, vp, vp],

@@ -354,13 +354,19 @@ class PaliGemmaEngine:
     def gemma_prefill(self, x_resid: torch.Tensor, positions: torch.Tensor, cache: KVStore, B: int, L: int,
                       logits_rows: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                       want_hidden: bool = False, want_logits: bool = True, taps: Optional[list] = None,
-                      kv_rows: Optional[torch.Tensor] = None):
+                      kv_rows: Optional[torch.Tensor] = None, prefix_rows: Optional[torch.Tensor] = None,
+                      return_rows: bool = False):
         """GemmaForCausalLM.forward after the *sqrt(H) (modeling_gemma.py:510-534) on resid fp32 [B*L][H]
         (already scaled).  Fills cache slots [0, L).  logits_rows: int32 rows to emit logits for (None = all).
         kv_rows (int32 [B] on the device; a right-padded batch): row b's queries attend its first kv_rows[b] keys
-        only (ops.attention_rows); the padding's own rows compute finite values nobody reads."""
+        only (ops.attention_rows); the padding's own rows compute finite values nobody reads.
+        prefix_rows (int32 [B] on the device, with kv_rows): row b is a prefix-LM sequence -- its first prefix_rows[b]
+        positions attend one another, the later ones causally (ops.attention_prefix; score()).
+        return_rows: also return the final norm's bf16 rows [rows][H] (the lm_head's input), as a third value."""
         if kv_rows is not None and mask is not None:
             raise ValueError("gemma_prefill: per-row key counts replace the additive mask, pass one of them")
+        if prefix_rows is not None and (kv_rows is None or mask is not None):
+            raise ValueError("gemma_prefill: prefix_rows needs kv_rows (each row's length) and excludes the additive mask")
         w = self.w
         T = B * L
         H, I, nh, nkv, hd = w.hidden, w.inter, w.heads, w.kv_heads, w.head_dim
@@ -387,7 +393,10 @@ class PaliGemmaEngine:
             self._lin(xin, Lw, "qkv", qb, ops.EPI_QKV_ROPE, T, fa=fa)
             a_args = (qb, nh * hd, attn, attn.stride(0), cache.k[i], cache.Smax * kvd, hd, kvd,
                       cache.vt[i], kvd * cache.Smax, hd * cache.Smax, cache.Smax)
-            if kv_rows is not None:
+            if prefix_rows is not None:
+                ops.attention_prefix(*a_args, B=B, Lq=L, Lkv=L, lkv_rows=kv_rows, prefix_rows=prefix_rows, Hq=nh,
+                                     Hkv=nkv, D=hd, scale=1.0 / math.sqrt(hd), **ks_t)
+            elif kv_rows is not None:
                 ops.attention_rows(*a_args, B=B, Lq=L, Lkv=L, lkv_rows=kv_rows, Hq=nh, Hkv=nkv, D=hd,
                                    scale=1.0 / math.sqrt(hd), **ks_t)
             else:
@@ -416,7 +425,7 @@ class PaliGemmaEngine:
         ops.norm_residual(x_resid, w.final_w, mode=ops.NORM_RMS, partials=part, nsplit=ns, out=xf, out_f32=hid,
                           row_map=logits_rows, write_resid=False)
         logits = self.lm_head(xf, rows, fresh=True) if want_logits else None
-        return logits, hid
+        return (logits, hid, xf) if return_rows else (logits, hid)
 
     def _key_split_args(self, tag: str, B: int, Lq: int, Lkv: int, Hq: int, Hkv: int, D: int) -> dict:
         """pg_attention keyword arguments for a key-split prefill attention (ops.prefill_key_splits; {} = unsplit):
@@ -1089,6 +1098,104 @@ class PaliGemmaEngine:
         logits, _ = self.gemma_prefill(resid, pos, cache, B, L, logits_rows=rows.contiguous(), kv_rows=lens)
         nxt = am.sum(-1).to(torch.int32) + 1                              # modeling_paligemma.py:189
         return cache, feats, logits, nxt
+
+    # ------------------------------------------------------------------ scoring a given answer
+    SCORE_CHUNK_ROWS = 128  # answer rows per lm_head + token_logprob launch pair: one reused [chunk][V] fp32 buffer
+    # rows every score lm_head launch computes at least: one more than the GEMV takes, so always the tile GEMM (score())
+    _SCORE_MIN_M = ops.GEMV_MAX_M + 1
+
+    @staticmethod
+    def score_spans(attention_mask: torch.Tensor, token_type_ids: torch.Tensor):
+        """(prefix lengths, row lengths), int64 [B] on the host, of a scoring batch: row b is [prefix_b | suffix_b | pad]
+        with the mask right-padded (mask_lengths) and token_type_ids 0 over the prefix, 1 over the suffix, 0 over the
+        padding.  Raises ValueError -- before anything is launched -- for type ids whose ones are not one run ending at
+        the row's length, for a row without a suffix, and for a suffix that starts at position 0."""
+        lens = mask_lengths(attention_mask)
+        if tuple(token_type_ids.shape) != tuple(attention_mask.shape):
+            raise ValueError(f"token_type_ids {tuple(token_type_ids.shape)} must match attention_mask "
+                             f"{tuple(attention_mask.shape)}")
+        t = token_type_ids.detach().to("cpu") != 0
+        n1 = t.sum(-1)
+        if bool((n1 == 0).any()):
+            raise ValueError(f"token_type_ids: row {int((n1 == 0).nonzero()[0])} has an empty suffix (no token of type 1)")
+        prefix = lens - n1
+        idx = torch.arange(t.shape[1])[None, :]
+        want = (idx >= prefix[:, None]) & (idx < lens[:, None])
+        if not torch.equal(t, want):
+            bad = int((t != want).any(-1).nonzero()[0])
+            raise ValueError(f"token_type_ids: row {bad}'s ones are not one contiguous run ending at the row's length "
+                             f"{int(lens[bad])} (prefix 0s, suffix 1s, padding 0s)")
+        if bool((prefix < 1).any()):
+            raise ValueError(f"token_type_ids: row {int((prefix < 1).nonzero()[0])}'s suffix starts at position 0 "
+                             "(nothing to condition the first answer token on)")
+        return prefix, lens
+
+    def score(self, input_ids: torch.Tensor, pixel_values: torch.Tensor, attention_mask: torch.Tensor,
+              token_type_ids: torch.Tensor, return_logits: bool = False) -> dict:
+        """Log-probabilities of given answers: row b of input_ids is [prefix_b | suffix_b | pad] (image + prompt, then
+        the answer; score_spans' layout).  One prefix-LM prefill over all rows -- prefix positions attend one another,
+        answer positions causally (ops.attention_prefix), positions as in prefill_request -- then the final norm, the
+        lm_head and pg_token_logprob on the rows that predict an answer token only: position p predicts token p + 1,
+        so row b contributes positions prefix_b - 1 .. len_b - 2.  Those rows run in chunks of SCORE_CHUNK_ROWS through
+        one logits buffer (a long answer never holds rows x V fp32), every launch on the bf16 tile GEMM with at least
+        ops.GEMV_MAX_M + 1 = 17 rows (a chunk shorter than that also runs the rows after it -- the row list is padded
+        by 16 -- instead of switching to the GEMV, whose sums differ in the last bits): the result does not depend on
+        the chunk size.  The price is a short answer's: 17 lm_head rows where one would do (scripts/tune/score_bench.py
+        times both).
+
+        Returns {"logprobs": fp32 [B][S_max], 0 past a row's answer; "top1": int64 [B][S_max] the model's own greedy
+        token at each answer position, the pad id past it; "suffix_lens": int64 [B]; with return_logits also "logits":
+        fp32 [sum S_b][V], row b's answer rows after row b - 1's}."""
+        B, L = input_ids.shape
+        prefix_h, lens_h = self.score_spans(attention_mask, token_type_ids)       # host checks, before any launch
+        if self.tp > 1:
+            raise NotImplementedError("score() is not supported under tensor parallelism (tp > 1)")
+        w = self.w
+        dev = self.device
+        suf = lens_h - prefix_h
+        S_max, R = int(suf.max()), int(suf.sum())
+        b_of = torch.repeat_interleave(torch.arange(B), suf)                       # [R] batch row of each answer token
+        j_of = torch.arange(R) - torch.repeat_interleave(torch.cumsum(suf, 0) - suf, suf)     # its index in the answer
+        p_of = prefix_h[b_of] + j_of                                               # its position in the row
+        ids = input_ids.to(dev)
+        targets = ids[b_of.to(dev), p_of.to(dev)].to(torch.int64).contiguous()
+        pad_rows = max(0, self._SCORE_MIN_M - 1)        # so that a last chunk of one row still has 17 rows to run
+        row_map = torch.cat([b_of * L + p_of - 1, torch.zeros(pad_rows, dtype=torch.int64)])
+        row_map = row_map.to(device=dev, dtype=torch.int32).contiguous()
+
+        feats = self.vision(pixel_values)
+        cache = self.new_cache(B, L + 1)
+        resid = self._buf("p_resid", (B * L, w.hidden), torch.float32)
+        self.embed_merge(ids, feats, resid)
+        am = attention_mask.to(dev)
+        pos = am.cumsum(-1).masked_fill(am == 0, 1)                                # modeling_paligemma.py:195
+        _, _, xf = self.gemma_prefill(resid, pos, cache, B, L, logits_rows=row_map, want_logits=False,
+                                      kv_rows=lens_h.to(device=dev, dtype=torch.int32).contiguous(),
+                                      prefix_rows=prefix_h.to(device=dev, dtype=torch.int32).contiguous(),
+                                      return_rows=True)                          # xf: the normalised rows [R + pad][H]
+
+        logprob = torch.empty(R, dtype=torch.float32, device=dev)
+        top1 = torch.empty(R, dtype=torch.int64, device=dev)
+        out_logits = torch.empty(R, w.vocab, dtype=torch.float32, device=dev) if return_logits else None
+        chunk = max(1, int(self.SCORE_CHUNK_ROWS))
+        buf = self._buf("score_logits", (max(chunk, self._SCORE_MIN_M), w.vocab_local_pad), torch.float32)
+        ws = self._buf("score_ws", (ops.token_logprob_workspace(chunk),), torch.uint8)
+        for r0 in range(0, R, chunk):
+            n = min(chunk, R - r0)
+            m = max(n, self._SCORE_MIN_M)
+            ops.gemm(xf[r0:r0 + m], w.lm_w, buf[:m], epi=ops.EPI_F32 | w.wflag, bias=w.lm_bias)
+            ops.token_logprob(buf[:n], targets[r0:r0 + n], logprob[r0:r0 + n], top1[r0:r0 + n], ws, V=w.vocab)
+            if return_logits:
+                out_logits[r0:r0 + n].copy_(buf[:n, :w.vocab])
+        pad = self.pad_id if self.pad_id >= 0 else 0
+        lp = torch.zeros(B, S_max, dtype=torch.float32, device=dev)
+        t1 = torch.full((B, S_max), pad, dtype=torch.int64, device=dev)
+        lp[b_of.to(dev), j_of.to(dev)] = logprob
+        t1[b_of.to(dev), j_of.to(dev)] = top1
+        out = {"logprobs": lp, "top1": t1, "suffix_lens": suf.clone()}
+        if return_logits:
+            out["logits"] = out_logits
+        return out
 
     def generate(self, input_ids, pixel_values, attention_mask, max_new_tokens: int, do_sample=False,
                  temperature=0.8, top_p=0.9, uniforms=None, stop_token: Optional[int] = 1, use_graph=True,

@@ -322,6 +322,20 @@ def attention_rows(q, q_rs, o, o_rs, k, k_bs, k_hs, k_rs, vt, vt_bs, vt_hs, vt_d
               _p(part_o), _p(part_ml), int(kcap), _p(kd), _p(vd), _s())
 
 
+def attention_prefix(q, q_rs, o, o_rs, k, k_bs, k_hs, k_rs, vt, vt_bs, vt_hs, vt_ds, *, B, Lq, Lkv, lkv_rows,
+                     prefix_rows, Hq, Hkv, D, scale, mask=None, mask_bs=0, mask_rs=0, nsplit=0, part_o=None,
+                     part_ml=None):
+    """Prefix-LM prefill attention (pg_attention_prefix): attention_rows() in prefill mode plus prefix_rows int32 [B] on
+    the device.  Row b's query at position p attends key j iff j < min(len_b, max(prefix_b, p + 1)), len_b =
+    lkv_rows[b] clamped to [1, Lkv], prefix_b = prefix_rows[b] clamped to [1, len_b]: the first prefix_b positions
+    attend one another fully, the positions after them causally.  prefix_rows == lkv_rows gives attention_rows' bits."""
+    _chk_rows(lkv_rows, B, "lkv_rows")
+    _chk_rows(prefix_rows, B, "prefix_rows")
+    _lib.call("pg_attention_prefix", _p(q), q_rs, _p(o), o_rs, _p(k), k_bs, k_hs, k_rs, _p(vt), vt_bs, vt_hs, vt_ds,
+              _p(mask), mask_bs, mask_rs, B, Lq, Lkv, _p(lkv_rows), _p(prefix_rows), Hq, Hkv, D, float(scale), 0,
+              nsplit, _p(part_o), _p(part_ml), 0, None, None, _s())
+
+
 def decode_cache_pack(k: torch.Tensor, vt: torch.Tensor, Hkv: int):
     """The decode-order copies (kd, vd) [B][Hkv][Smax][D] of a canonical cache (k [B][Smax][Hkv*D], vt [B][Hkv*D][Smax])
     -- what the QKV epilogue writes beside the canonical cache (csrc/attn_common.h dec_koff / dec_voff); for tests
@@ -469,6 +483,46 @@ def argmax(logits, out_ids, workspace, *, hist=None, step=None, pos=None, kv_len
               _p(step), _p(pos), _p(kv_len), _s())
 
 
+TOKEN_LOGPROB_CHUNKS = 64   # workgroups a row is split over (csrc/misc.hip TL_CHUNKS)
+
+
+def token_logprob_workspace(R: int) -> int:
+    """Bytes of workspace pg_token_logprob needs for R rows: per row and chunk the running (max, sum, argmax), and
+    the row's target logit."""
+    return R * (TOKEN_LOGPROB_CHUNKS * 12 + 4)
+
+
+def token_logprob(logits, targets, logprob, top1=None, workspace=None, *, V: Optional[int] = None):
+    """logprob[r] = logits[r][targets[r]] - logsumexp(logits[r][:V]) in fp32 (pg_token_logprob); top1 (optional,
+    int64 [R]) the row's argmax, lowest index on ties.  logits fp32 [R][>= V] with unit column stride, targets int64
+    [R]; a target outside [0, V) gives -inf.  workspace: uint8, token_logprob_workspace(R) bytes (allocated when
+    not given).  Returns logprob."""
+    _chk(logits, torch.float32, "logits")
+    _chk(targets, torch.int64, "targets")
+    _chk(logprob, torch.float32, "logprob")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("pghip.token_logprob: logits must be [R][V] with unit column stride")
+    R = logits.shape[0]
+    V = logits.shape[1] if V is None else V
+    if not 0 < V <= logits.shape[1] or R < 1 or (R > 1 and logits.stride(0) < V):
+        raise ValueError(f"pghip.token_logprob: V = {V} of {logits.shape[1]} columns, R = {R}, row stride "
+                         f"{logits.stride(0)}")
+    if not targets.is_contiguous() or targets.numel() < R or not logprob.is_contiguous() or logprob.numel() < R:
+        raise ValueError("pghip.token_logprob: targets and logprob must be contiguous with R entries")
+    if top1 is not None:
+        _chk(top1, torch.int64, "top1")
+        if not top1.is_contiguous() or top1.numel() < R:
+            raise ValueError("pghip.token_logprob: top1 must be contiguous int64 with R entries")
+    need = token_logprob_workspace(R)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=logits.device)
+    elif not workspace.is_cuda or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"pghip.token_logprob: workspace smaller than {need} bytes")
+    _lib.call("pg_token_logprob", _p(logits), max(logits.stride(0), V), R, V, _p(targets), _p(logprob), _p(top1),
+              _p(workspace), _s())
+    return logprob
+
+
 def argmax_embed(logits, out_ids, workspace, embed, feat, n_feat, res, *, image_id, pad_id, img_scale, normalizer,
                  hist=None, step=None, pos=None, kv_len=None):
     """argmax + the next step's input rows res[b] = embed_merge(winner_b) (one launch fewer per decode step)."""
@@ -576,6 +630,10 @@ def split_for(tiles: int, k_steps: int, target: int = 256, max_split: int = 4) -
 
 
 CUS = 256   # MI355X compute units
+# pg_gemm / pg_gemm_fused run up to this many rows on the weight-streaming GEMV and more on the tile GEMM (csrc/gemm.hip
+# gemm_impl: M <= 16).  The two sum K in different orders, so a caller that needs a row's bits not to depend on how
+# many rows share its launch (PaliGemmaEngine.score's chunks) stays on one side of it.
+GEMV_MAX_M = 16
 
 
 def gemm_ksplit(M: int, N: int, K: int) -> int:

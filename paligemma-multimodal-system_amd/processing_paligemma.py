@@ -84,25 +84,44 @@ class PaliGemmaProcessor:
         toks = self.tokenizer(s, return_tensors="pt", truncation=truncation, padding=padding)
         return {"pixel_values": pixel_values, **toks}
 
-    def batch(self, images: List, texts: List[str]) -> dict:
+    def batch(self, images: List, texts: List[str], suffixes: Optional[List[str]] = None) -> dict:
         """Several (image, prompt) pairs as one right-padded batch for ``generate`` (the reference handles one pair,
         its ``__call__`` asserts so): each pair goes through ``__call__`` alone -- so every row's ids are exactly its
         single-request ids, quirks included -- and the rows are padded on the right with the tokenizer's pad id to
         the longest.  Returns stacked ``pixel_values`` [B][3][S][S], ``input_ids`` [B][L] and ``attention_mask``
         [B][L] (ones over a row's own tokens, zeros over its padding); ``generate`` then gives every row what it
-        gives that pair alone."""
+        gives that pair alone.
+
+        suffixes (one answer per pair, for ``score``): row b is its single-request ids followed by the tokenised
+        answer and ``<eos>``, and the result also holds ``token_type_ids`` [B][L]: 0 over the prompt row, 1 over the
+        answer and its ``<eos>``, 0 over the padding.  Without suffixes the result is what it was."""
         if len(images) != len(texts) or not len(images):
             raise ValueError(f"batch: {len(images)} images for {len(texts)} prompts (need one prompt per image)")
+        if suffixes is not None and len(suffixes) != len(texts):
+            raise ValueError(f"batch: {len(suffixes)} suffixes for {len(texts)} prompts (need one answer per prompt)")
         pad = self.tokenizer.pad_token_id
         if pad is None:
             raise ValueError("batch: the tokenizer has no pad token to pad the shorter prompts with")
         rows = [self([im], [tx]) for im, tx in zip(images, texts)]
-        L = max(r["input_ids"].shape[1] for r in rows)
+        tails = [[] for _ in rows]
+        if suffixes is not None:
+            eos = self.tokenizer.eos_token_id
+            if eos is None:
+                raise ValueError("batch: the tokenizer has no eos token to end the answers with")
+            tails = [list(self.tokenizer(sx, add_special_tokens=False)["input_ids"]) + [eos] for sx in suffixes]
+        L = max(r["input_ids"].shape[1] + len(t) for r, t in zip(rows, tails))
         ids = torch.full((len(rows), L), pad, dtype=rows[0]["input_ids"].dtype)
         mask = torch.zeros(len(rows), L, dtype=rows[0]["attention_mask"].dtype)
-        for b, r in enumerate(rows):
+        types = torch.zeros(len(rows), L, dtype=rows[0]["input_ids"].dtype)
+        for b, (r, t) in enumerate(zip(rows, tails)):
             n = r["input_ids"].shape[1]
             ids[b, :n] = r["input_ids"][0]
             mask[b, :n] = r["attention_mask"][0]
-        return {"pixel_values": torch.cat([r["pixel_values"] for r in rows]), "input_ids": ids,
-                "attention_mask": mask}
+            if t:
+                ids[b, n:n + len(t)] = torch.tensor(t, dtype=ids.dtype)
+                mask[b, n:n + len(t)] = 1
+                types[b, n:n + len(t)] = 1
+        out = {"pixel_values": torch.cat([r["pixel_values"] for r in rows]), "input_ids": ids, "attention_mask": mask}
+        if suffixes is not None:
+            out["token_type_ids"] = types
+        return out
