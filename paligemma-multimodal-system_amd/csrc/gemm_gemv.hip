@@ -402,7 +402,9 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ A, int lda,
   if constexpr (EPI == PG_EPI_F32_FIN) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const int n0 = min((tile0 + t) * 16, e.N - 16) + 4 * g;
+      // the lane's own four columns (tile * 16 + q, as the epilogue stores them); a lane past the row's end -- a tile
+      // past the last, or the tail of a ragged last tile (N % 16 != 0) -- reads the row's last four, unused
+      const int n0 = min((tile0 + t) * 16 + 4 * g, e.N - 4);
       const size_t ro = (size_t)(r < M ? r : M - 1) * e.N + n0;
       // both loads unconditional (a branch or select on them here would make the compiler wait for them before
       // the weight stream): without fx the fixed-point pair reads fin_resid's first 32 bytes, unused; fin_base picks
