@@ -353,6 +353,40 @@ int pg_argmax_embed(const float* logits, long ld, int B, int V, void* workspace,
 int pg_token_logprob(const float* logits, long ld, int R, int V, const int64_t* targets, float* logprob,
                      int64_t* top1, void* workspace, hipStream_t stream);
 
+/* (added under ABI 13; the version stays 13, nothing existing changed)  Beam search, one selection step for B prompts
+ * of W beams each; rows bW .. bW + W - 1 are prompt b's group.  logits fp32 [B*W][ld] (ld >= V; 16-B loads where the
+ * rows allow them, read once; a row is split over 64 workgroups).  Candidates of a group: a live parent p offers
+ * (p, t) for every t in [0, V) with score cum[p] + log_softmax(logits[p][0:V])[t] in fp32; a finished parent offers
+ * (p, pad_token) with score cum[p] alone.  The best W are kept, best first; exact fp32 ties go to the lower (p, t)
+ * (within a row candidates are pre-selected by logit, lowest index among equals, as pg_argmax); a NaN score never
+ * beats a comparable one (-inf included); a row of nothing but -inf scores -inf.  Row o = bW + rank receives
+ * out_ids[o] (int64, always in [0, V)), parent[o] (int32, a global row index inside the group), cum[o] and
+ * finished[o] = the parent's flag, or 1 when the token is stop_token (negative: none) -- cum and finished are updated
+ * in place: the partial launch only reads them, and the final launch, one workgroup, reads a group's values in the
+ * wave that owns the group before that wave writes any of them.  Decode-state advance as pg_argmax: hist_tok[*step][o]
+ * and hist_parent[*step][o] (both nullable, [hist_rows][B*W], written only while *step < hist_rows), pos[o] += 1,
+ * *kv_len += 1, *step += 1 (each nullable).  flag (nullable): one word, 1 when every row is finished, else 0.
+ * workspace: B*W * (64 * 8 + 64 * W * 8 + W * 8 + 8) bytes rounded up to 32, 16-B aligned.  1 <= W <= 8, W <= V, B*W <= 1024, 0 <= pad_token
+ * < V, stop_token < V; anything else returns hipErrorInvalidValue before any launch.  Deterministic run to run. */
+int pg_beam_select(const float* logits, long ld, int V, int B, int W, float* cum, int* finished, int stop_token,
+                   int pad_token, void* workspace, int64_t* out_ids, int* parent, int64_t* hist_tok,
+                   int* hist_parent, int hist_rows, int* step, int* pos, int* kv_len, int* flag, hipStream_t stream);
+/* (added under ABI 13)  Reorder the generated suffix of a KV cache after a beam selection, all layers in one call:
+ * for every layer and row r, positions [base[r], len[r]) of row r become what row parent[r] held there before the
+ * call, in k [layers][rows][Smax][Hkv*D], vt [layers][rows][Hkv*D][Smax] and the decode-order copies kd / vd
+ * [layers][rows][Hkv][Smax][D] (csrc/attn_common.h dec_koff / dec_voff) alike.  len[r] = len_base + len_dev[r]
+ * (len_rows != 0) or len_base + len_dev[0] (one word for the batch): the decode step's slot_dev / slot_base after its
+ * sampler has advanced them.  The copy moves whole 32-key blocks, [floor32(base[r]), ceil32(len[r])): the positions
+ * below base must be equal in r and parent[r] (beams share their prompt), those from len on are dead until appended
+ * to.  Everything else, and every row with parent[r] == r or len[r] <= base[r], keeps its bytes; a parent outside
+ * [0, rows) is treated as r.  Any parent map is legal (swaps, cycles, one parent for all): launch 1 copies the windows
+ * into scratch, launch 2 copies them back into place.  scratch: 4 * layers * rows * S_scr * Hkv * D bf16, 16-B aligned, holding S_scr
+ * (a multiple of 32) positions per row: S_scr >= ceil32(len) - floor32(base) for every row the caller will ever pass
+ * (a window is cut to S_scr).  The grid is fixed by S_scr and Smax, the work by the device-side lengths. */
+int pg_kv_beam_gather(void* k, void* vt, void* kd, void* vd, int layers, int rows, int Smax, int Hkv, int D,
+                      const int* parent, const int* base, const int* len_dev, int len_rows, int len_base,
+                      void* scratch, int S_scr, hipStream_t stream);
+
 /* vocabulary-parallel greedy for tensor parallelism: local (max, first global index) pairs [B][2] of a
  * vocab shard starting at vocab_offset; after an all-gather, pg_argmax_merge takes the global winner
  * (lowest index on ties, as torch.argmax) and advances the decode state like pg_argmax. */

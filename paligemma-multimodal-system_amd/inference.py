@@ -50,9 +50,20 @@ def _sample_top_p(probs: torch.Tensor, p: float):
 
 def test_inference(model: PaliGemmaForConditionalGeneration, processor: PaliGemmaProcessor, device: str,
                    prompt: str, image_file_path: str, max_tokens_to_generate: int, temperature: float,
-                   top_p: float, do_sample: bool):
-    """Generate until EOS or max_tokens_to_generate, then print prompt + decoded (inference.py:29-87)."""
+                   top_p: float, do_sample: bool, num_beams: int = 1):
+    """Generate until EOS or max_tokens_to_generate, then print prompt + decoded (inference.py:29-87).  num_beams > 1
+    (not in the reference): beam search instead, the best hypothesis printed (greedy within the beams: do_sample,
+    temperature and top_p do not apply)."""
     inputs = get_model_inputs(processor, prompt, image_file_path, device)
+    if num_beams != 1:
+        if do_sample:
+            raise ValueError("--num_beams searches deterministically; drop --do_sample")
+        res = model.generate_beam(inputs["input_ids"], inputs["pixel_values"], inputs["attention_mask"],
+                                  max_new_tokens=max_tokens_to_generate, num_beams=num_beams,
+                                  stop_token=processor.tokenizer.eos_token_id)
+        ids = torch.tensor([res["sequences"][0][0]], dtype=torch.int64)
+        print(prompt + processor.tokenizer.decode(ids[0], skip_special_tokens=True))
+        return ids
     ids = model.generate(inputs["input_ids"], inputs["pixel_values"], inputs["attention_mask"],
                          max_new_tokens=max_tokens_to_generate, do_sample=do_sample, temperature=temperature,
                          top_p=top_p, stop_token=processor.tokenizer.eos_token_id)
@@ -62,7 +73,8 @@ def test_inference(model: PaliGemmaForConditionalGeneration, processor: PaliGemm
 
 
 def main(model_path: str = None, prompt: str = None, image_file_path: str = None, max_tokens_to_generate: int = 100,
-         temperature: float = 0.8, top_p: float = 0.9, do_sample: bool = False, only_cpu: bool = False):
+         temperature: float = 0.8, top_p: float = 0.9, do_sample: bool = False, only_cpu: bool = False,
+         num_beams: int = 1):
     if only_cpu:
         raise RuntimeError("this build has no CPU path (HIP kernels only); drop --only_cpu")
     if not torch.cuda.is_available():
@@ -80,7 +92,7 @@ def main(model_path: str = None, prompt: str = None, image_file_path: str = None
     print("Running inference")
     with torch.no_grad():
         test_inference(model, processor, device, prompt, image_file_path, max_tokens_to_generate, temperature,
-                       top_p, do_sample)
+                       top_p, do_sample, num_beams=num_beams)
 
 
 def _bool(s) -> bool:
@@ -99,6 +111,8 @@ def _cli(argv=None):
     ap.add_argument("--top_p", type=float, default=0.9)
     ap.add_argument("--do_sample", type=_bool, default=False)
     ap.add_argument("--only_cpu", type=_bool, default=False)
+    ap.add_argument("--num_beams", type=int, default=1, help="beam search with this many beams (1: the greedy / "
+                    "sampling loop)")
     a = ap.parse_args(argv)
     main(**vars(a))
 

@@ -193,6 +193,22 @@ class PaliGemmaForConditionalGeneration(nn.Module):
         return eng.score(input_ids, pixel_values, attention_mask, token_type_ids, return_logits=return_logits)
 
     @torch.no_grad()
+    def generate_beam(self, input_ids, pixel_values, attention_mask=None, max_new_tokens: int = 100, num_beams: int = 4,
+                      length_penalty: float = 1.0, num_return_sequences: int = 1, stop_token: Optional[int] = 1,
+                      pad_token: int = 0, **kw) -> dict:
+        """Beam search (what `num_beams` asks of transformers' generate, in the frozen-beam variant: a finished beam
+        keeps its place and score instead of moving to a hypothesis heap; see PaliGemmaEngine.generate_beam).  Prompts
+        as generate takes them; returns the engine's dict: "sequences" (per prompt num_return_sequences id lists, best
+        first, each ending at its stop token), "scores" (sum of log-probabilities / length ** length_penalty) and
+        "sum_logprobs", fp32 [B][num_return_sequences]."""
+        eng = self.engine(input_ids.device)
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        return eng.generate_beam(input_ids, pixel_values, attention_mask, max_new_tokens, num_beams,
+                                 length_penalty=length_penalty, num_return_sequences=num_return_sequences,
+                                 stop_token=stop_token, pad_token=pad_token, **kw)
+
+    @torch.no_grad()
     def generate(self, input_ids, pixel_values, attention_mask=None, max_new_tokens: int = 100,
                  do_sample: bool = False, temperature: float = 0.8, top_p: float = 0.9, uniforms=None,
                  stop_token: Optional[int] = 1):

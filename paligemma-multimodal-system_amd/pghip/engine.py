@@ -110,6 +110,19 @@ class KVStore:
         for t_new, t_old in ((self.kd, old.kd), (self.vd, old.vd)):   # [layers][B][Hkv][Smax][hd] (dec_koff / voff)
             t_new.view(-1, self.B, hk, self.Smax, hd)[:nl, :, :, :nb] = t_old.view(nl, old.B, hk, old.Smax, hd)[:, :, :, :nb]
 
+    def repeat_rows(self, W: int) -> "KVStore":
+        """A store of B * W rows whose row b * W + w is a copy of this store's row b, in all four layouts (beam search:
+        every beam of a prompt starts from the prompt's cache).  Once per request, plain copies."""
+        new = KVStore.__new__(KVStore)
+        new.B, new.Smax, new.kv_dim, new.kv_heads = self.B * W, self.Smax, self.kv_dim, self.kv_heads
+        nl = self.k.shape[0]
+        new.k = self.k.repeat_interleave(W, dim=1).contiguous()
+        new.vt = self.vt.repeat_interleave(W, dim=1).contiguous()
+        new.kd = self.kd.view(nl, self.B, -1).repeat_interleave(W, dim=1).reshape(nl, -1).contiguous()
+        new.vd = self.vd.view(nl, self.B, -1).repeat_interleave(W, dim=1).reshape(nl, -1).contiguous()
+        new.length, new.ragged = self.length, self.ragged
+        return new
+
 
 class PaliGemmaEngine:
     DECODE_SPLIT_O = 2      # split-K of o_proj at decode (B > FUSE_MAX_B: more workgroups for the batched GEMV)
@@ -646,7 +659,8 @@ class PaliGemmaEngine:
 
     # ------------------------------------------------------------------ decode step (graph-capturable)
     def _chain_ok(self, sampler) -> bool:
-        return self.CHAIN_EMBED and self.tp == 1 and sampler is not None and not sampler.get("do_sample")
+        return (self.CHAIN_EMBED and self.tp == 1 and sampler is not None and not sampler.get("do_sample")
+                and sampler.get("beam") is None)      # a beam step re-embeds st["ids"]: its rows change hypothesis
 
     def decode_state(self, B: int, cache: KVStore, positions_next: torch.Tensor, max_steps: int, sampler=None):
         """Device-resident decode state: ids, positions, kv length, step counter, token history.
@@ -1058,6 +1072,8 @@ class PaliGemmaEngine:
                feats: Optional[torch.Tensor] = None):
         """Next ids from logits [B][V] (greedy or top-p); advance=True also moves pos / kv_len on.  A chained
         state (decode_state) also gets the next step's input rows: pass the request's image features."""
+        if sampler.get("beam") is not None:
+            return self._beam_sample(logits, st, sampler["beam"], advance)
         kw = dict(hist=st["hist"], step=st["step"])
         if advance:     # (per-row lengths: pos[b] is the row's length too, and the samplers leave a null kv_len alone)
             kw.update(pos=st["pos"], kv_len=None if st.get("ragged") else st["kv_len"])
@@ -1071,6 +1087,23 @@ class PaliGemmaEngine:
                             top_p=sampler["top_p"], **kw)
         else:
             ops.argmax(logits, st["ids"], st["ws"], **kw)
+
+    def _beam_sample(self, logits: torch.Tensor, st: dict, bm: dict, advance: bool):
+        """The beam sampler: pg_beam_select on the step's logits (ids, parents, scores, finished flags, both histories
+        and the state advance), then -- once the step has appended a key -- pg_kv_beam_gather, so that row r's
+        generated keys and values are those of the hypothesis it now continues."""
+        ragged = bool(st.get("ragged"))
+        kw = dict(hist_tok=st["hist"], hist_parent=bm["hist_parent"], step=st["step"], flag=bm["flag"])
+        if advance:
+            kw.update(pos=st["pos"], kv_len=None if ragged else st["kv_len"])
+        ops.beam_select(logits, bm["cum"], bm["finished"], st["ids"], bm["parent"], bm["ws"], W=bm["W"],
+                        V=self.w.vocab, stop_token=bm["stop_token"], pad_token=bm["pad_token"], **kw)
+        bm["logits"] = logits                       # (a static buffer: the trace copies it after each step)
+        if advance:
+            c = bm["cache"]
+            ops.kv_beam_gather(c.k, c.vt, c.kd, c.vd, bm["parent"], bm["base"],
+                               st["pos"] if ragged else st["kv_len"], bm["scratch"], kv_heads=c.kv_heads,
+                               len_rows=ragged, len_base=-1 if ragged else 0, S_scr=bm["S_scr"])
 
     # ------------------------------------------------------------------ full request
     def prefill_request(self, input_ids: torch.Tensor, pixel_values: torch.Tensor, attention_mask: torch.Tensor,
@@ -1259,6 +1292,152 @@ class PaliGemmaEngine:
             out[b, : len(r)] = torch.tensor(r, dtype=torch.int64)
         return out
 
+    @staticmethod
+    def beam_args(num_beams, num_return_sequences, max_new_tokens, vocab: int, length_penalty=1.0):
+        """Host checks of generate_beam's arguments (ValueError before anything is launched)."""
+        if not isinstance(num_beams, int) or not 1 <= num_beams <= ops.BEAM_MAX_W:
+            raise ValueError(f"num_beams must be an integer in 1..{ops.BEAM_MAX_W}, got {num_beams!r}")
+        if num_beams > vocab:
+            raise ValueError(f"num_beams {num_beams} exceeds the vocabulary ({vocab})")
+        if not isinstance(num_return_sequences, int) or not 1 <= num_return_sequences <= num_beams:
+            raise ValueError(f"num_return_sequences must be in 1..num_beams = {num_beams}, got {num_return_sequences!r}")
+        if not isinstance(max_new_tokens, int) or max_new_tokens < 1:
+            raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens!r}")
+        if not math.isfinite(float(length_penalty)):
+            raise ValueError(f"length_penalty must be finite, got {length_penalty!r}")
+
+    @staticmethod
+    def beam_backtrack(hist_tok, hist_parent, row: int) -> list:
+        """The tokens of the hypothesis that ends in `row` after the last recorded step: hist_tok / hist_parent are
+        [steps][rows] lists (or arrays), parents global row indices."""
+        out, cur = [], row
+        for t in range(len(hist_tok) - 1, -1, -1):
+            out.append(int(hist_tok[t][cur]))
+            cur = int(hist_parent[t][cur])
+        return out[::-1]
+
+    def beam_begin(self, input_ids, pixel_values, attention_mask, max_new_tokens: int, W: int, stop_token=1,
+                   pad_token: int = 0, lens_h=None):
+        """What generate_beam sets up before its loop: the prefill of the B prompts, the B * W-row cache whose row
+        bW + w is prompt b's (KVStore.repeat_rows), the decode state, the beam sampler (scores, finished flags,
+        parents, the parent history, the selection workspace and the gather's scratch), and the first selection, on
+        the prefill logits.  Returns (state, cache, image features, sampler): decode_step(state, cache, feats, sampler)
+        is then one beam step (scripts/tune/beam_bench.py times it)."""
+        w, dev = self.w, self.device
+        lens_h = mask_lengths(attention_mask) if lens_h is None else lens_h
+        rows = input_ids.shape[0] * W
+        cache0, feats, logits0, nxt = self.prefill_request(input_ids, pixel_values, attention_mask, max_new_tokens)
+        cache = cache0.repeat_rows(W)
+        del cache0
+        S_scr = _rup(max_new_tokens + 1, 32) + 32       # ceil32(base + new) - floor32(base) for any base
+        base_h = lens_h.repeat_interleave(W)
+        lo = int(base_h.min()) // 32 * 32
+        bm = dict(W=W, stop_token=stop_token, pad_token=int(pad_token), cache=cache, S_scr=S_scr,
+                  cum=torch.full((rows,), float("-inf"), dtype=torch.float32, device=dev),
+                  finished=torch.zeros(rows, dtype=torch.int32, device=dev),
+                  parent=torch.zeros(rows, dtype=torch.int32, device=dev),
+                  hist_parent=torch.zeros(max_new_tokens + 1, rows, dtype=torch.int32, device=dev),
+                  flag=torch.zeros(1, dtype=torch.int32, device=dev),
+                  base=base_h.to(device=dev, dtype=torch.int32).contiguous(),
+                  ws=torch.empty(ops.beam_select_workspace(rows, W), dtype=torch.uint8, device=dev),
+                  scratch=torch.empty(ops.kv_beam_gather_scratch(w.t_layers, rows, S_scr, cache.kv_dim),
+                                      dtype=torch.bfloat16, device=dev),
+                  # what the first decode step's gather can touch (the graph warm-up restores it)
+                  warm_window=(lo, min(cache.Smax, _rup(int(base_h.max()) + 1, 32))))
+        bm["cum"][::W] = 0.0
+        sampler = dict(do_sample=False, beam=bm)
+        st = self.decode_state(rows, cache, nxt.repeat_interleave(W), max_new_tokens, sampler=sampler)
+        # the first selection, on the prefill logits (each prompt's row given to all its beams; only beam 0 can win)
+        self.sample(logits0[:, :w.vocab].repeat_interleave(W, dim=0).contiguous(), st, sampler, advance=False)
+        return st, cache, feats, sampler
+
+    def generate_beam(self, input_ids, pixel_values, attention_mask, max_new_tokens: int, num_beams: int,
+                      length_penalty: float = 1.0, num_return_sequences: int = 1, stop_token: Optional[int] = 1,
+                      pad_token: int = 0, use_graph=True, check_every: Optional[int] = None,
+                      return_trace: bool = False) -> dict:
+        """Beam search for B >= 1 right-padded prompts (as generate takes them), W = num_beams hypotheses each.
+
+        The frozen-beam variant, NOT transformers' hypothesis heap: every decision stays on the device, so a step is
+        one graph.  The W beams of prompt b are rows bW .. bW + W - 1 of an ordinary batched decode step over a cache
+        whose rows are copies of the prompt's.  A hypothesis's score is the fp32 sum of its tokens' log-probabilities
+        (log-softmax of the step's fp32 logits, no temperature); beam 0 starts at 0 and the others at -inf, so the
+        first selection, on the prefill logits, keeps the top W first tokens.  Per step and prompt a live beam offers
+        every token, a finished beam (one that took stop_token; None: nothing finishes) only (itself, pad_token) at an
+        unchanged score; the best W candidates are kept, best first, exact ties to the lower (beam, token)
+        (pg_beam_select), and each row's generated keys and values follow its hypothesis (pg_kv_beam_gather).  The run
+        ends when every beam of every prompt is finished (read every check_every steps) or at max_new_tokens.  Final
+        score = sum / n ** length_penalty, n = tokens up to and including the stop token (max_new_tokens for an
+        unfinished beam); the best num_return_sequences per prompt are returned, best first, ties to the lower beam.
+        num_beams = 1 generates exactly generate's greedy ids.
+
+        Returns {"sequences": per prompt a list of id lists, each ending at its stop token; "scores": fp32 [B][R];
+        "sum_logprobs": fp32 [B][R]; "beam_rows": int64 [B][R] the final row of each}; with return_trace also "tokens",
+        "parents" (int64 [steps][B*W]), "cum" (fp32 [steps][B*W]) and "logits" (a list of fp32 [B*W][V] per step)."""
+        w = self.w
+        self.beam_args(num_beams, num_return_sequences, max_new_tokens, w.vocab, length_penalty)
+        lens_h = mask_lengths(attention_mask)                   # host check, before any launch
+        if not 0 <= int(pad_token) < w.vocab or (stop_token is not None and not 0 <= int(stop_token) < w.vocab):
+            raise ValueError(f"pad_token {pad_token} / stop_token {stop_token} outside the vocabulary ({w.vocab})")
+        if self.tp > 1:
+            raise NotImplementedError("generate_beam is not supported under tensor parallelism (tp > 1)")
+        B, W, R = input_ids.shape[0], num_beams, num_return_sequences
+        rows = B * W
+        if rows > ops.BEAM_MAX_ROWS:
+            raise ValueError(f"{B} prompts x {W} beams = {rows} rows, more than {ops.BEAM_MAX_ROWS}")
+        st, cache, feats, sampler = self.beam_begin(input_ids, pixel_values, attention_mask, max_new_tokens, W,
+                                                    stop_token=stop_token, pad_token=pad_token, lens_h=lens_h)
+        bm = sampler["beam"]
+        trace = {"cum": [bm["cum"].clone()], "logits": [bm["logits"][:, :w.vocab].clone()]} if return_trace else None
+
+        def record():
+            if trace is not None:
+                trace["logits"].append(bm["logits"][:, :w.vocab].clone())
+                trace["cum"].append(bm["cum"].clone())
+
+        n = 1
+        step_fn = None
+        if use_graph and self.comm.capturable and max_new_tokens > 1:
+            step_fn = self._graph_step(st, cache, feats, sampler)
+        if step_fn is None:
+            step_fn = lambda: self.decode_step(st, cache, feats, sampler)  # noqa: E731
+        if check_every is None:
+            check_every = 1 if rows == 1 else 8
+        while n < max_new_tokens:
+            if stop_token is not None and n % check_every == 0 and int(bm["flag"].item()):
+                break
+            step_fn()
+            record()
+            n += 1
+        hist_tok = st["hist"][:n].cpu()
+        hist_par = bm["hist_parent"][:n].cpu().to(torch.int64)
+        cum = bm["cum"].cpu()
+        self.check_numerics()
+        tok_l, par_l = hist_tok.tolist(), hist_par.tolist()
+        seqs, scores, sums, brow = [], [], [], []
+        for b in range(B):
+            hyp = []
+            for wi in range(W):
+                r = b * W + wi
+                toks = self.beam_backtrack(tok_l, par_l, r)
+                if stop_token is not None and stop_token in toks:
+                    toks = toks[: toks.index(stop_token) + 1]
+                    cnt = len(toks)
+                else:
+                    cnt = max_new_tokens
+                c = float(cum[r])
+                hyp.append((c / float(cnt) ** float(length_penalty), wi, toks, c))
+            # best first; NaN last; ties to the lower beam (a stable sort over beams in order)
+            hyp.sort(key=lambda h: (h[0] != h[0], -h[0] if h[0] == h[0] else 0.0))
+            seqs.append([h[2] for h in hyp[:R]])
+            scores.append([h[0] for h in hyp[:R]])
+            sums.append([h[3] for h in hyp[:R]])
+            brow.append([b * W + h[1] for h in hyp[:R]])
+        out = {"sequences": seqs, "scores": torch.tensor(scores, dtype=torch.float32),
+               "sum_logprobs": torch.tensor(sums, dtype=torch.float32), "beam_rows": torch.tensor(brow, dtype=torch.int64)}
+        if trace is not None:
+            out.update(tokens=hist_tok, parents=hist_par, cum=torch.stack(trace["cum"]).cpu(), logits=trace["logits"])
+        return out
+
     def _graph_step(self, st, cache, feats, sampler):
         """Capture one decode step into a hipGraph (warm-up run first, on a side stream)."""
         torch.cuda.synchronize()
@@ -1266,6 +1445,15 @@ class PaliGemmaEngine:
         snap = {k: st[k].clone() for k in ("ids", "pos", "kv_len", "step")}
         hist0 = st["hist"].clone()
         res0 = self._ws["d_res_a"][: st["ids"].numel() * self.w.hidden].clone() if st.get("chain") else None
+        bm = sampler.get("beam") if sampler is not None else None
+        if bm is not None:      # the beam state the warm-up step advances, and the cache window its gather permutes
+            bsnap = {k: bm[k].clone() for k in ("cum", "finished", "parent", "hist_parent", "flag")}
+            lo, hi = bm["warm_window"]
+            kv5 = lambda t: t.view(cache.k.shape[0], cache.B, cache.kv_heads, cache.Smax, -1)  # noqa: E731
+            csnap = [(cache.k[:, :, lo:hi], cache.k[:, :, lo:hi].clone()),
+                     (cache.vt[..., lo:hi], cache.vt[..., lo:hi].clone()),
+                     (kv5(cache.kd)[:, :, :, lo:hi], kv5(cache.kd)[:, :, :, lo:hi].clone()),
+                     (kv5(cache.vd)[:, :, :, lo:hi], kv5(cache.vd)[:, :, :, lo:hi].clone())]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         try:
@@ -1279,6 +1467,11 @@ class PaliGemmaEngine:
             st["hist"].copy_(hist0)
             if res0 is not None:                    # the chained input rows the warm-up step overwrote
                 self._ws["d_res_a"][: res0.numel()].copy_(res0)
+            if bm is not None:
+                for k, v in bsnap.items():
+                    bm[k].copy_(v)
+                for dst, src in csnap:
+                    dst.copy_(src)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self.decode_step(st, cache, feats, sampler)

@@ -523,6 +523,104 @@ def token_logprob(logits, targets, logprob, top1=None, workspace=None, *, V: Opt
     return logprob
 
 
+BEAM_MAX_W = 8              # beams per prompt pg_beam_select takes (csrc/beam.hip BS_MAXW)
+BEAM_MAX_ROWS = 1024        # ... and rows (prompts x beams) per call
+BEAM_CHUNKS = 64            # workgroups a row is split over (csrc/beam.hip BS_CHUNKS)
+
+
+def beam_select_workspace(rows: int, W: int) -> int:
+    """Bytes of workspace pg_beam_select needs for rows = prompts x W: per row and chunk the running (max, sum) and the
+    chunk's best W candidates (64-bit words), then per row its best W and its (max, log sum)."""
+    if not 1 <= W <= BEAM_MAX_W or rows < 1 or rows % W:
+        raise ValueError(f"pghip.beam_select_workspace: rows = {rows}, W = {W} (1 <= W <= {BEAM_MAX_W}, rows % W == 0)")
+    up16 = lambda x: (x + 15) // 16 * 16  # noqa: E731
+    return up16(rows * BEAM_CHUNKS * 8) + rows * BEAM_CHUNKS * W * 8 + rows * W * 8 + up16(rows * 8)
+
+
+def beam_select(logits, cum, finished, out_ids, parent, workspace=None, *, W: int, V: Optional[int] = None,
+                stop_token: Optional[int] = None, pad_token: int = 0, hist_tok=None, hist_parent=None, step=None,
+                pos=None, kv_len=None, flag=None):
+    """One beam-search selection (pg_beam_select): logits fp32 [B*W][>= V], rows bW..bW+W-1 prompt b's beams; cum fp32
+    and finished int32 [B*W] are read and updated in place; out_ids int64 and parent int32 [B*W] receive the kept
+    candidates, best first per prompt.  A finished beam offers (itself, pad_token) with its score unchanged; exact
+    ties go to the lower (parent, token).  hist_tok int64 / hist_parent int32 [steps][B*W], step, pos, kv_len: the
+    decode-state advance of argmax; flag int32 [1]: 1 when every row is finished."""
+    _chk(logits, torch.float32, "logits")
+    _chk(cum, torch.float32, "cum")
+    _chk(finished, torch.int32, "finished")
+    _chk(out_ids, torch.int64, "out_ids")
+    _chk(parent, torch.int32, "parent")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("pghip.beam_select: logits must be [B*W][V] with unit column stride")
+    rows = logits.shape[0]
+    V = logits.shape[1] if V is None else V
+    if not 1 <= W <= BEAM_MAX_W or W > V or rows % W or not 0 < rows <= BEAM_MAX_ROWS:
+        raise ValueError(f"pghip.beam_select: W = {W}, V = {V}, rows = {rows}: needs 1 <= W <= {BEAM_MAX_W}, W <= V, "
+                         f"rows a multiple of W and at most {BEAM_MAX_ROWS}")
+    if not 0 < V <= logits.shape[1] or (rows > 1 and logits.stride(0) < V):
+        raise ValueError(f"pghip.beam_select: V = {V} of {logits.shape[1]} columns, row stride {logits.stride(0)}")
+    stop = -1 if stop_token is None else int(stop_token)
+    if not 0 <= pad_token < V or stop >= V:
+        raise ValueError(f"pghip.beam_select: pad_token {pad_token} / stop_token {stop_token} outside [0, {V})")
+    for t, name in ((cum, "cum"), (finished, "finished"), (out_ids, "out_ids"), (parent, "parent")):
+        if not t.is_contiguous() or t.numel() != rows:
+            raise ValueError(f"pghip.beam_select: {name} must be contiguous with {rows} entries")
+    if hist_tok is not None:
+        _chk(hist_tok, torch.int64, "hist_tok")
+    if hist_parent is not None:
+        _chk(hist_parent, torch.int32, "hist_parent")
+    hr = [_rows(t, rows) for t in (hist_tok, hist_parent) if t is not None]
+    for t, name in ((step, "step"), (pos, "pos"), (kv_len, "kv_len"), (flag, "flag")):
+        if t is not None:
+            _chk(t, torch.int32, name)
+    if pos is not None and pos.numel() < rows:
+        raise ValueError("pghip.beam_select: pos must hold one entry per row")
+    need = beam_select_workspace(rows, W)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=logits.device)
+    elif not workspace.is_cuda or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"pghip.beam_select: workspace smaller than {need} bytes")
+    _lib.call("pg_beam_select", _p(logits), max(logits.stride(0), V), V, rows // W, W, _p(cum), _p(finished), stop,
+              int(pad_token), _p(workspace), _p(out_ids), _p(parent), _p(hist_tok), _p(hist_parent),
+              min(hr) if hr else 0, _p(step), _p(pos), _p(kv_len), _p(flag), _s())
+
+
+def kv_beam_gather_scratch(layers: int, rows: int, S_scr: int, kv_dim: int) -> int:
+    """bf16 elements of scratch kv_beam_gather needs to move windows of up to S_scr positions (a multiple of 32)."""
+    return 4 * layers * rows * S_scr * kv_dim
+
+
+def kv_beam_gather(k, vt, kd, vd, parent, base, len_dev, scratch, *, kv_heads: int, len_rows: bool, len_base: int,
+                   S_scr: int):
+    """Reorder a KV cache's generated suffix after a beam selection (pg_kv_beam_gather): positions [base[r], len[r]) of
+    row r, in every layer, become row parent[r]'s, in k [layers][rows][Smax][kvd], vt [layers][rows][kvd][Smax] and the
+    decode-order copies kd / vd [layers][rows * Smax * kvd].  len[r] = len_base + len_dev[r] (len_rows) or len_base +
+    len_dev[0].  Whole 32-key blocks move (floor32(base) .. ceil32(len)); scratch: bf16,
+    kv_beam_gather_scratch(layers, rows, S_scr, kvd) elements."""
+    for t, name in ((k, "k"), (vt, "vt"), (kd, "kd"), (vd, "vd"), (scratch, "scratch")):
+        _chk(t, torch.bfloat16, name)
+        if not t.is_contiguous():
+            raise ValueError(f"pghip.kv_beam_gather: {name} must be contiguous")
+    for t, name in ((parent, "parent"), (base, "base"), (len_dev, "len_dev")):
+        _chk(t, torch.int32, name)
+        if not t.is_contiguous():
+            raise ValueError(f"pghip.kv_beam_gather: {name} must be contiguous")
+    if k.dim() != 4 or vt.dim() != 4:
+        raise ValueError("pghip.kv_beam_gather: k must be [layers][rows][Smax][kvd], vt [layers][rows][kvd][Smax]")
+    layers, rows, Smax, kvd = k.shape
+    if tuple(vt.shape) != (layers, rows, kvd, Smax) or kd.numel() != k.numel() or vd.numel() != k.numel():
+        raise ValueError("pghip.kv_beam_gather: the four cache layouts differ in size")
+    if kvd % kv_heads or (kvd // kv_heads) % 8 or Smax % 32 or S_scr % 32 or S_scr < 32:
+        raise ValueError(f"pghip.kv_beam_gather: kvd {kvd} / {kv_heads} heads, Smax {Smax}, S_scr {S_scr}: head_dim "
+                         "must be a multiple of 8, Smax and S_scr multiples of 32")
+    if parent.numel() != rows or base.numel() != rows or len_dev.numel() < (rows if len_rows else 1):
+        raise ValueError("pghip.kv_beam_gather: parent / base need one entry per row, len_dev one per row or one word")
+    if scratch.numel() < kv_beam_gather_scratch(layers, rows, S_scr, kvd):
+        raise ValueError("pghip.kv_beam_gather: scratch too small")
+    _lib.call("pg_kv_beam_gather", _p(k), _p(vt), _p(kd), _p(vd), layers, rows, Smax, kv_heads, kvd // kv_heads,
+              _p(parent), _p(base), _p(len_dev), int(bool(len_rows)), int(len_base), _p(scratch), S_scr, _s())
+
+
 def argmax_embed(logits, out_ids, workspace, embed, feat, n_feat, res, *, image_id, pad_id, img_scale, normalizer,
                  hist=None, step=None, pos=None, kv_len=None):
     """argmax + the next step's input rows res[b] = embed_merge(winner_b) (one launch fewer per decode step)."""
