@@ -13,67 +13,27 @@
 // inside the k-step is permuted to match, SURVEY/guide 'accumulator as operand') and
 // V^T from a transposed image (Vt[d][key], written transposed by the producer).
 //
-// Modes: normal (prefill): a wave walks all keys and writes normalised bf16 O;
-// split (decode): each wave owns a key range and writes (O, m, l) partials that
-// pg_attn_combine merges.
+// Modes (attn_form picks the kernel from the shapes):
+//   prefill  a wave walks all keys of its 16 query rows and writes normalised bf16 O: attn_fa_kernel (LDS-DMA flash,
+//            every unmasked call; with key splits it writes (O, m, l) partials that attn_pf_combine_kernel merges),
+//            and under an additive mask or a device kv length attn_lds_kernel (from 1024 16-row groups on) or the
+//            one-wave attn_kernel;
+//   decode   each wave owns a key range and writes (O, m, l) partials that pg_attn_combine or the o_proj prologue
+//            merges: attn_decode_kernel (one wave per split) and attn_decode_wg_kernel (2 / 4 waves per split, head_dim
+//            256); pg_attn_decode's attn_decode_fused_kernel (B > 2) merges inside the launch.
+// Measured alternatives to every constant here are in DESIGN §A.
 #include "attn_common.h"
 
-// waves per workgroup in split (decode) mode: tuning knob (scripts/tune/), 1 = one split per workgroup
-#ifndef PG_ATTN_FA
-#define PG_ATTN_FA 1      // prefill: the LDS-DMA flash kernel (0: the register-staged kernels)
-#endif
-#ifndef PG_FA_W12
-#define PG_FA_W12 1       // prefill, head_dim 256: 12-wave workgroups when they fill the one-per-CU rounds better
-#endif
-#ifndef PG_FA_W8R2
-#define PG_FA_W8R2 1      // head_dim 256: 8 waves x 2 row groups (256 rows per workgroup) on 32-key blocks
-#endif
-#ifndef PG_FA_W8R2_NST
-#define PG_FA_W8R2_NST 2  // (4 / 5 stages measured 4-5% slower at pt-896 x32)
-#endif
-#ifndef PG_FA_W8R2_HOIST
-#define PG_FA_W8R2_HOIST 4
-#endif
-#ifndef PG_FA_UNROLL
-#define PG_FA_UNROLL 1
-#endif
-#ifndef PG_FA_MASK_BRANCH
-#define PG_FA_MASK_BRANCH 1
-#endif
-#ifndef PG_FA_STAGE32
-#define PG_FA_STAGE32 1
-#endif
 #ifndef PG_FA_LAZY
 #define PG_FA_LAZY 0      // lazy rescale threshold (log2); 8 measured faster but failed the pt-896 fp8 bound
 #endif
-#ifndef PG_FA_PRIO
-#define PG_FA_PRIO 0
-#endif
-#ifndef PG_COMBINE_PF
-#define PG_COMBINE_PF 12  // split-KV merge: O partials of the first 12 splits per thread loaded up front
-#endif
 #define PG_ATTN_PIPE 0x100 // pg_attn_decode: flag OR-ed into nw -- the double-buffered form (include/pghip.h)
-#ifndef PG_ATTN_WG
-#define PG_ATTN_WG 1      // decode splits of 2 / 4 / 8 blocks (head_dim 256): one wave per block, merged in LDS
-#endif
-#ifndef PG_ATTN_SPLIT_WAVES
-#define PG_ATTN_SPLIT_WAVES 1
-#endif
-#ifndef PG_FA_DEEP
-#define PG_FA_DEEP 0      // 4-wave prefill workgroups: a 5-8 stage ring; measured slower (pt-224 Gemma 25.2 vs 22.7 us,
-                          // SigLIP 10.0 vs 10.0: not latency-bound; profiles/r03_prefill_breakdown_pt224.txt)
-#endif
-#ifndef PG_FA_SMALL
-#define PG_FA_SMALL 0     // 1 = batch-1 prefill grids in 1- / 2-wave workgroups: measured slower (pt-224 prefill 5.69 vs
-                          // 5.47 ms: a lone wave's staging latency is exposed; Gemma 33.0 vs 22.7 us, SigLIP 13.6 vs 10.0)
-#endif
 
 // Decode (split mode): one wave per (batch, kv head, split); grid (1, Hkv * nsplit, B).
 template <int DP, int DT, bool FULL>
 __global__ __launch_bounds__(64) void attn_decode_kernel(AttnArgs a) {
   const int nsplit = (int)gridDim.y / a.Hkv;
-  attn_decode_split<DP, DT, false, FULL>(a, blockIdx.z, blockIdx.y / nsplit, blockIdx.y % nsplit, nsplit,
-                                         threadIdx.x);
+  attn_decode_split<DP, DT, FULL>(a, blockIdx.z, blockIdx.y / nsplit, blockIdx.y % nsplit, nsplit, threadIdx.x);
 }
 
 // Decode (split mode) with NW * NB-block splits (split_keys = 32 * NW * NB): one workgroup of NW waves per (batch,
@@ -165,13 +125,6 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_wg_kernel(AttnArgs a) {
 // PIPE: each wave's blocks are staggered -- the next block's K / V loads are issued between the current block's
 // phases, so its loads never drain during a compute phase (one wave per SIMD at pt-896 x32: each round's compute,
 // 0.9 us, stalled the stream of the single-buffered form).
-#ifndef PG_DEC_SHARE_MERGE
-#define PG_DEC_SHARE_MERGE 1
-#endif
-// splits whose partials the merging workgroup loads per round trip (8: the engine's split cap, no clamped duplicates)
-#ifndef PG_DEC_MERGE_MCH
-#define PG_DEC_MERGE_MCH 8
-#endif
 template <int DP, int DT, int NW, bool PIPE>
 __global__ __launch_bounds__(NW * 64, 2) void attn_decode_fused_kernel(AttnArgs a, int nb, int* __restrict__ cnt,
                                                                       uint8_t* __restrict__ q8, float* __restrict__ q8s,
@@ -295,7 +248,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_decode_fused_kernel(AttnArgs 
   // the NW waves' (O, m, l) -> the split's partial, 2^(m_w - M) weights.  SHARE (4 waves, DT % 4 == 0): every wave
   // publishes its (O, m, l) and merges and stores a quarter of the columns (the same sum order as one wave merging
   // all of them, so the same bits), so the partial's stores drain from four waves before the ticket
-  constexpr bool SHARE = PG_DEC_SHARE_MERGE && NW == 4 && DT % 4 == 0;
+  constexpr bool SHARE = NW == 4 && DT % 4 == 0;
   constexpr int NSO = SHARE ? NW : (NW > 1 ? NW - 1 : 1);
   __shared__ f32x4 so[NSO][DT][64];
   __shared__ float sml[NSO][2][16];
@@ -378,8 +331,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_decode_fused_kernel(AttnArgs 
 #endif
   if (!s_last) return;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");        // compiler-only: the loads stay below the ticket
-  // the last split's workgroup merges the S partials: one thread per (q row, 8 dims), MCH (8) splits per round trip
-  constexpr int D8 = DP / 8, MCH = PG_DEC_MERGE_MCH;
+  // the last split's workgroup merges the S partials: one thread per (q row, 8 dims), MCH splits per round trip
+  // (8: the engine's split cap, no clamped duplicates)
+  constexpr int D8 = DP / 8, MCH = 8;
   u32x4 pk = {0u, 0u, 0u, 0u};                      // this thread's last 8 outputs (the fp8 copy below)
   for (int it = threadIdx.x; it < G * D8; it += NW * 64) {
     const int r = it / D8, d8 = it % D8;
@@ -454,6 +408,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_decode_fused_kernel(AttnArgs 
 #endif
 }
 
+// One-wave prefill attention (an additive mask or a device kv length, fewer than 1024 16-row groups): one wave, 16 query
+// rows, per workgroup; K rows and V^T runs straight from memory, one round trip per 32-key block.
 // PFX (pg_attention_prefix): the wave walks the keys its last position sees and each query masks at its own count.
 template <int DP, int DT, bool PFX = false>
 __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
@@ -462,28 +418,13 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
   const int wave = threadIdx.x >> 6;
   const int c = lane & 15;
   const int g = lane >> 4;
-  const int b = blockIdx.z;
-  const bool split = a.split_keys > 0;
-  const int wpg = (int)(blockDim.x >> 6);
-  const int nsg = split ? (int)(gridDim.y / a.Hkv) : 1;
-  const int kvh = blockIdx.y / nsg;
-  const int sg = blockIdx.y % nsg;
+  const int b = blockIdx.z, kvh = blockIdx.y;
   const int Lkv = attn_prefill_keys(a, b);
   const int R = a.Lq * a.G;
   const int D = a.D;
-
-  if (split) {
-    attn_decode_split<DP, DT, false>(a, b, kvh, sg * wpg + wave, nsg * wpg, lane);
-    return;
-  }
-  const int r0 = split ? 0 : (blockIdx.x * (int)(blockDim.x >> 6) + wave) * 16;
-  int kbeg = 0, kend = Lkv, sp = 0;
-  if (split) {
-    sp = sg * wpg + wave;
-    kbeg = sp * a.split_keys;
-    kend = min(Lkv, kbeg + a.split_keys);
-  }
-  if (!split && r0 >= R) return;
+  const int r0 = (blockIdx.x * (int)(blockDim.x >> 6) + wave) * 16;
+  int kend = Lkv;
+  if (r0 >= R) return;
 
   const int r = r0 + c;
   const bool rvalid = r < R;
@@ -500,10 +441,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
   {
     const bf16_t* qp = a.q + ((long)b * a.Lq + pos) * a.q_rs + (long)hq * D;
 #pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int d0 = 32 * s + 8 * g;
-      qf[s] = __builtin_bit_cast(bf16x8, ld16_sel(qp + (d0 < D ? d0 : 0), rvalid && d0 < D));
-    }
+    for (int s = 0; s < KS; ++s) qf[s] = attn_q_frag(qp, 32 * s + 8 * g, D, rvalid);
   }
   const bf16_t* kbase = a.k + (long)b * a.k_bs + (long)kvh * a.k_hs;
   const bf16_t* vbase = a.vt + (long)b * a.vt_bs + (long)kvh * a.vt_hs;
@@ -515,7 +453,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
   float m = -INFINITY, l = 0.f;
   const float LOG2E = 1.4426950408889634f;
 
-  for (int kb = kbeg; kb < kend; kb += 32) {
+  for (int kb = 0; kb < kend; kb += 32) {
     // issue every load of the block first (K rows for S^T, V^T rows for P.V): one memory round trip
     // K rows past kend are clamped to a valid row: their scores are masked to -inf below
     const int ka = min(kb + c, kend - 1), kbk = min(kb + 16 + c, kend - 1);
@@ -589,30 +527,17 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
   }
 
   // lane holds O^T[d = 16t + 4g + j][q = c]
-  if (!split) {
-    if (!rvalid) return;
-    const float inv = 1.0f / l;
-    bf16_t* op = a.o + ((long)b * a.Lq + pos) * a.o_rs + (long)hq * D;
+  if (!rvalid) return;
+  const float inv = 1.0f / l;
+  bf16_t* op = a.o + ((long)b * a.Lq + pos) * a.o_rs + (long)hq * D;
 #pragma unroll
-    for (int t = 0; t < DT; ++t) {
-      const int d = 16 * t + 4 * g;
-      if (d < D) {
-        u32x2 p;
-        p[0] = pack_bf2(o[t][0] * inv, o[t][1] * inv);
-        p[1] = pack_bf2(o[t][2] * inv, o[t][3] * inv);
-        *(u32x2*)(op + d) = p;
-      }
-    }
-  } else {
-    const int nsplit = nsg * wpg;
-    const long base = (((long)b * a.Hkv + kvh) * nsplit + sp) * 16 + c;
-    if (!rvalid) return;                       // rows past Lq*G are never merged
-    float* po = a.part_o + base * (DT * 16);
-#pragma unroll
-    for (int t = 0; t < DT; ++t) *(f32x4*)(po + 16 * t + 4 * g) = o[t];
-    if (g == 0) {
-      a.part_ml[base * 2 + 0] = m;
-      a.part_ml[base * 2 + 1] = l;
+  for (int t = 0; t < DT; ++t) {
+    const int d = 16 * t + 4 * g;
+    if (d < D) {
+      u32x2 p;
+      p[0] = pack_bf2(o[t][0] * inv, o[t][1] * inv);
+      p[1] = pack_bf2(o[t][2] * inv, o[t][3] * inv);
+      *(u32x2*)(op + d) = p;
     }
   }
 }
@@ -657,10 +582,7 @@ __global__ __launch_bounds__(256) void attn_lds_kernel(AttnArgs a) {
   {
     const bf16_t* qp = a.q + ((long)b * a.Lq + pos) * a.q_rs + (long)hq * D;
 #pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int d0 = 32 * s + 8 * g;
-      qf[s] = __builtin_bit_cast(bf16x8, ld16_sel(qp + (d0 < D ? d0 : 0), rvalid && d0 < D));
-    }
+    for (int s = 0; s < KS; ++s) qf[s] = attn_q_frag(qp, 32 * s + 8 * g, D, rvalid);
   }
   const bf16_t* kbase = a.k + (long)b * a.k_bs + (long)kvh * a.k_hs;
   const bf16_t* vbase = a.vt + (long)b * a.vt_bs + (long)kvh * a.vt_hs;
@@ -797,8 +719,7 @@ __global__ __launch_bounds__(256) void attn_lds_kernel(AttnArgs a) {
 // (16 query rows each) walks KB-key blocks (KB 64 or 32); every block's K [KB keys][DP] and V^T [DT*16 d][KB keys]
 // are pulled HBM->LDS by global_load_lds (16 B/lane, lane-linear destinations) into an NST-stage ring: NST - 1
 // blocks in flight while one is computed, the wait for a block a counted vmcnt (its younger blocks stay in flight
-// across the barrier).  NST 2 / KB 64 for grids that fill the chip; a deep ring (NST 5-8) for the batch-1 grids
-// of a few dozen workgroups, whose time is otherwise one L2 round trip per block.  Images:
+// across the barrier).  Launched with NST 2: KB 64, and KB 32 for the 8 x 2 form of head_dim 256.  Images:
 //   K   : 16-key groups of [DP/8 chunks][16 keys][16 B] -> a S^T fragment read (16 keys x 32 d) is one
 //         contiguous KiB per wave-instruction (conflict-free ds_read_b128).  Image row i of group kt holds key
 //         32 (kt / 2) + 8 (i / 4) + 4 (kt % 2) + i % 4 (the source address picks it), so the S^T lanes of a
@@ -829,7 +750,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
   constexpr int VIMG = DT * 16 * VROW;
   constexpr int STAGE = KIMG + VIMG;
   constexpr int KINS = KIMG / 1024, VINS = VIMG / 1024;   // glds wave-instructions per block
-  constexpr int FA_HOIST = (DP == 256 && WAVES == 8 && RPW == 2) ? PG_FA_W8R2_HOIST : 0;
+  constexpr int FA_HOIST = (DP == 256 && WAVES == 8 && RPW == 2) ? 4 : 0;
   // lazy rescale (tuning knob, off): head_dim >= 128 only -- at head_dim 72 the rescale is cheap and the branch cost
   // more (pt-896 x32 SigLIP 3.79 -> 3.89 ms; Gemma 4.96 -> 4.75 ms)
   constexpr int LAZY = DP >= 128 ? PG_FA_LAZY : 0;
@@ -860,10 +781,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
     hq[i] = kvh * a.G + (rvalid[i] ? r % a.G : 0);
     const bf16_t* qp = a.q + ((long)b * a.Lq + pos[i]) * a.q_rs + (long)hq[i] * D;
 #pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int d0 = 32 * s + 8 * g;
-      qf[i][s] = __builtin_bit_cast(bf16x8, ld16_sel(qp + (d0 < D ? d0 : 0), rvalid[i] && d0 < D));
-    }
+    for (int s = 0; s < KS; ++s) qf[i][s] = attn_q_frag(qp, 32 * s + 8 * g, D, rvalid[i]);
   }
   // keys the workgroup walks (kwalk), keys every row of this wave sees (kfull: blocks below it are not masked) and
   // keys each lane's queries see (vis); all three are the row's length unless PFX
@@ -892,19 +810,17 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
       // chunks past D (D < DP) re-read chunk 0: the matching q dims are zero, and 0 * (finite K) = 0, whereas
       // the bytes past a head's D may be another tensor's never-written memory (NaN * 0 = NaN)
       const int kr = min(kb + key, Lkv - 1), kc = ch * 8 < D ? ch * 8 : 0;
-      // (PG_FA_STAGE32: uniform base + 32-bit lane offset -- the saddr form, no 64-bit address arithmetic per piece;
-      // the host takes this kernel only where a head's K rows and V^T rows span < 4 GiB)
-      const bf16_t* src = PG_FA_STAGE32 ? (const bf16_t*)((const char*)kbase + ((unsigned)kr * (unsigned)a.k_rs + (unsigned)kc) * 2u)
-                                        : kbase + (long)kr * a.k_rs + kc;
-      __builtin_amdgcn_global_load_lds((const void*)src, (LDS_AS void*)(kimg + i * 1024), 16, 0, 0);
+      // (uniform base + 32-bit lane offset -- the saddr form, no 64-bit address arithmetic per piece; the host takes
+      // this kernel only where a head's K rows and V^T rows span < 4 GiB)
+      const void* src = (const char*)kbase + ((unsigned)kr * (unsigned)a.k_rs + (unsigned)kc) * 2u;
+      __builtin_amdgcn_global_load_lds(src, (LDS_AS void*)(kimg + i * 1024), 16, 0, 0);
     }
     for (int i = wave; i < VINS; i += WAVES) {
       const int row = KB == 64 ? 8 * i + (lane >> 3) : 16 * i + (lane >> 2);
       const int cl = KB == 64 ? (lane & 7) ^ ((row >> 1) & 7) : (lane & 3) ^ ((row >> 2) & 2);
       const int vr = min(row, D - 1), vc = min(kb + 8 * cl, vkey_max);
-      const bf16_t* src = PG_FA_STAGE32 ? (const bf16_t*)((const char*)vbase + ((unsigned)vr * (unsigned)a.vt_ds + (unsigned)vc) * 2u)
-                                        : vbase + (long)vr * a.vt_ds + vc;
-      __builtin_amdgcn_global_load_lds((const void*)src, (LDS_AS void*)(vimg + i * 1024), 16, 0, 0);
+      const void* src = (const char*)vbase + ((unsigned)vr * (unsigned)a.vt_ds + (unsigned)vc) * 2u;
+      __builtin_amdgcn_global_load_lds(src, (LDS_AS void*)(vimg + i * 1024), 16, 0, 0);
     }
   };
   // glds pieces this wave issues per block (wave-uniform): its vmcnt step per younger block in flight
@@ -928,11 +844,6 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
 #pragma unroll
   for (int sb = 0; sb < NST - 1; ++sb)
     if (sb < nblk) stage(kb0 + sb * KB, sb);
-  // static priority for the second-dispatched half of a 2-wave-per-SIMD workgroup (tuning knob)
-  if constexpr (PG_FA_PRIO) if (WAVES >= 8 && wave >= WAVES / 2) __builtin_amdgcn_s_setprio(1);
-#if PG_FA_UNROLL == 2
-#pragma unroll 2
-#endif
   for (int ib = 0; ib < nblk; ++ib) {
     const int kb = kb0 + ib * KB;
     // block ib has landed once at most (blocks issued after it) * P of this wave's pieces are outstanding
@@ -973,7 +884,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fa_kernel(AttnArgs a) {
       if (kb + KB > kfull) {
         // (the empty volatile asm keeps this a branch: if-converted, the ~50 compares and selects of the key mask ran
         // on every block, a third of the softmax's VALU)
-        if constexpr (PG_FA_MASK_BRANCH) asm volatile("");
+        asm volatile("");
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
@@ -1093,15 +1004,16 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
   const int b = bk / Hkv, kvh = bk % Hkv;
   __shared__ float wsh[256];
   __shared__ float inv_den;
-  // thread (sg, dq): dims 4dq..4dq+3, splits sg, sg+4, ...; the first PG_COMBINE_PF of its splits' O partials
+  // thread (sg, dq): dims 4dq..4dq+3, splits sg, sg+4, ...; the first PF (12) of its splits' O partials
   // are loaded before the (m, l) reduction (clamped addresses, discarded by a select later), so the usual
-  // split count (<= 4 * PG_COMBINE_PF) costs one memory round trip instead of two
+  // split count (<= 4 * PF) costs one memory round trip instead of two
   const int dq = threadIdx.x & 63, sg = threadIdx.x >> 6;
   const bool dok = 4 * dq < D;
   const float* po = part_o + ((long)bk * nsplit * 16 + row) * DTW + 4 * (dok ? dq : 0);
-  f32x4 pre[PG_COMBINE_PF > 0 ? PG_COMBINE_PF : 1];
+  constexpr int PF = 12;
+  f32x4 pre[PF];
 #pragma unroll
-  for (int i = 0; i < PG_COMBINE_PF; ++i) pre[i] = *(const f32x4*)(po + (long)min(sg + 4 * i, nsplit - 1) * 16 * DTW);
+  for (int i = 0; i < PF; ++i) pre[i] = *(const f32x4*)(po + (long)min(sg + 4 * i, nsplit - 1) * 16 * DTW);
   // split weights 2^(m_s - M) (thread s), and the denominator
   float ms = -INFINITY, ls = 0.f;
   if ((int)threadIdx.x < nsplit) {
@@ -1127,13 +1039,13 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
   f32x4 num = {0.f, 0.f, 0.f, 0.f};
   if (dok) {
 #pragma unroll
-    for (int i = 0; i < PG_COMBINE_PF; ++i) {
+    for (int i = 0; i < PF; ++i) {
       const int s2 = sg + 4 * i;
       const float wv = s2 < nsplit ? wsh[s2] : 0.f;
       num += wv != 0.f ? wv * pre[i] : f32x4{0.f, 0.f, 0.f, 0.f};   // empty splits hold no partials
     }
 #pragma unroll 4
-    for (int s2 = sg + 4 * PG_COMBINE_PF; s2 < nsplit; s2 += 4) {
+    for (int s2 = sg + 4 * PF; s2 < nsplit; s2 += 4) {
       const float wv = wsh[s2];
       const f32x4 pv = *(const f32x4*)(po + (long)s2 * 16 * DTW);
       num += wv != 0.f ? wv * pv : f32x4{0.f, 0.f, 0.f, 0.f};   // empty splits hold no partials
@@ -1196,106 +1108,107 @@ __global__ __launch_bounds__(256) void attn_pf_combine_kernel(const float* __res
   *(u32x2*)(o + ((long)b * Lq + pos) * o_rs + (long)hq * D + 4 * d4) = p;
 }
 
-// Flash attention, 16-row query groups per wave.  2 (one K / V^T fragment read feeding two row groups,
-// 4 waves at head_dim 256) measured 0.81x at pt-448 Gemma, 0.95x / 1.03x at SigLIP 448 / 896: default 1.
-#ifndef PG_FA_RPW
-#define PG_FA_RPW 1
-#endif
-
-// the deep ring of a 4-wave workgroup: 64-key blocks when >= 4 stages fit the 160 KiB of LDS, else 32-key blocks
-template <int DP, int DT>
-struct FaDeep {
-  static constexpr int S64 = 64 * DP * 2 + DT * 16 * 128, S32 = 32 * DP * 2 + DT * 16 * 64;
-  static constexpr int KB = 163840 / S64 >= 4 ? 64 : 32;
-  static constexpr int N = 163840 / (KB == 64 ? S64 : S32);
-  static constexpr int NST = N > 8 ? 8 : N;
+// The kernel form a pg_attention* call takes and its grid.
+enum AttnKind {
+  ATTN_FLASH,      // attn_fa_kernel, `waves` waves of `rpw` 16-row groups: 4x1, 8x1, and at head_dim 256 12x1 and 8x2
+  ATTN_LDS,        // attn_lds_kernel
+  ATTN_ONE_WAVE,   // attn_kernel
+  ATTN_DEC,        // attn_decode_kernel, not FULL
+  ATTN_DEC_FULL,   // attn_decode_kernel, FULL
+  ATTN_DEC_WG      // attn_decode_wg_kernel, `waves` 2 or 4 (head_dim 256 only)
+};
+struct AttnForm {
+  AttnKind kind;
+  int waves, rpw;
+  dim3 grid;
 };
 
-// the ring of the 8- / 12-wave workgroups (one per CU): KB-key blocks, as many stages as fit (capped at NST8)
-#ifndef PG_FA_KB8
-#define PG_FA_KB8 64
-#endif
-#ifndef PG_FA_NST8
-#define PG_FA_NST8 2
-#endif
-template <int DP, int DT>
-struct FaWide {
-  static constexpr int KB = PG_FA_KB8;
-  static constexpr int S = KB * DP * 2 + DT * 16 * KB * 2;
-  static constexpr int N = 163840 / S;
-  static constexpr int NST = N > PG_FA_NST8 ? PG_FA_NST8 : N;
-};
-
-// (PFX: the prefix-LM instances of pg_attention_prefix, the same forms)
-template <int DP, int DT, bool PFX>
-static void launch_fa(int waves, int rpw, bool deep, dim3 grid, hipStream_t stream, const AttnArgs& a) {
-  if (deep && waves == 4 && rpw == 1) {
-    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 4, 1, FaDeep<DP, DT>::KB, FaDeep<DP, DT>::NST, PFX>), grid, dim3(256), 0,
-                       stream, a);
-    return;
+// The form, from the shapes alone.  Prefill (split_keys == 0): the flash kernel where `flash` allows it (no mask, no
+// device kv length, 16-B aligned strides, 32-bit staging offsets), with the grid's x times nsplit key splits; else the
+// LDS-staged kernel from 1024 one-wave workgroups on (needs the aligned strides), else one wave per workgroup.
+// Decode (split_keys > 0): one workgroup per (batch, kv head, split).
+// (tests/test_score_gpu.py fa_form restates the wgs / rounds rules below, to know a shape's workgroup rows and key
+// block: a change of rule here is a change there)
+static AttnForm attn_form(int B, int Lq, int G, int Hkv, int D, int DP, bool flash, bool aligned, int split_keys,
+                          int nsplit, int kcap) {
+  const int R = Lq * G;
+  AttnForm f{ATTN_ONE_WAVE, 1, 1, dim3((R + 15) / 16, Hkv, B)};   // 16 query rows per workgroup: 4x the workgroups
+  if (split_keys > 0) {
+    f.grid = dim3(1, Hkv * nsplit, B);
+    const bool full = D == DP && kcap >= 32;       // the decode-order copies, no guards on loaded values
+    f.kind = full ? ATTN_DEC_FULL : ATTN_DEC;
+    // splits of 2 / 4 / 8 blocks at head_dim 256: one wave per block and round, merged in LDS
+    if (full && DP == 256 && (split_keys == 64 || split_keys % 128 == 0)) {
+      f.kind = ATTN_DEC_WG;
+      f.waves = split_keys == 64 ? 2 : 4;
+    }
+  } else if (flash) {
+    auto wgs = [&](int rows) { return (long)((R + rows - 1) / rows) * Hkv * B; };
+    auto rounds = [&](int rows) { return (wgs(rows) + 255) / 256; };
+    f.kind = ATTN_FLASH;
+    // head_dim 256, 8 waves x 2 row groups on 32-key blocks (twice the flops per LDS fragment read of 16-row waves, two
+    // waves per SIMD at 256 registers): one round costs ~1.55 of an 8 x 16-row round (pt-896 x32 Gemma 5.03 vs
+    // 6.29 ms), so it is taken where its rounds cost less than those of the 8- and 12-wave forms (pt-448 x16 keeps
+    // 12 waves: 3 rounds of 256 rows cost more than 3 of 192)
+    if (DP == 256 && wgs(256) >= 256 && rounds(256) * 25 < rounds(128) * 16 && rounds(256) * 25 < rounds(192) * 24) {
+      f.waves = 8;
+      f.rpw = 2;
+    } else {
+      // 8 waves (128 rows) per workgroup once that fills the chip
+      f.waves = wgs(128) >= 256 ? 8 : 4;
+      // head_dim 256 (166 VGPRs, fits 3 waves / SIMD): 12 waves when the one-workgroup-per-CU rounds cost
+      // less in total (pt-448 x16 Gemma: 688 workgroups in 3 rounds of 192 rows vs 1040 in 5 rounds of 128)
+      if (DP == 256 && f.waves == 8 && rounds(192) * 12 < rounds(128) * 8) f.waves = 12;
+    }
+    const int rows = 16 * f.waves * f.rpw;
+    f.grid = dim3((R + rows - 1) / rows * (nsplit > 1 ? nsplit : 1), Hkv, B);
+  } else if ((long)((R + 15) / 16) * Hkv * B >= 1024 && aligned) {
+    f.kind = ATTN_LDS;                             // 64 rows per workgroup share K / V^T
+    f.grid = dim3((R + 63) / 64, Hkv, B);
   }
-  if constexpr (PG_FA_RPW == 2) {
-    if constexpr (DP <= 96) {       // (DP 128 at 8 x 32 rows needs > 256 registers: 1 wave / SIMD)
-      if (waves == 8 && rpw == 2) {
-        hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 8, 2, 64, 2, PFX>), grid, dim3(512), 0, stream, a);
-        return;
-      }
-    }
-    if (waves == 4 && rpw == 2) {
-      hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 4, 2, 64, 2, PFX>), grid, dim3(256), 0, stream, a);
-      return;
-    }
-  }
-  if constexpr (DP == 256) {
-    if (waves == 8 && rpw == 2) {
-      hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 8, 2, 32, PG_FA_W8R2_NST, PFX>), grid, dim3(512), 0, stream, a);
-      return;
-    }
-    if (waves == 12) {
-      hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 12, 1, FaWide<DP, DT>::KB, FaWide<DP, DT>::NST, PFX>), grid, dim3(768),
-                         0, stream, a);
-      return;
-    }
-  }
-  if (waves == 8)
-    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 8, 1, FaWide<DP, DT>::KB, FaWide<DP, DT>::NST, PFX>), grid, dim3(512), 0,
-                       stream, a);
-  else if (waves == 2)
-    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 2, 1, 64, 2, PFX>), grid, dim3(128), 0, stream, a);
-  else if (waves == 1)
-    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 1, 1, 64, 2, PFX>), grid, dim3(64), 0, stream, a);
-  else
-    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 4, 1, 64, 2, PFX>), grid, dim3(256), 0, stream, a);
+  return f;
 }
 
-
-#define ATTN_DISPATCH(DP_, DT_)                                                             \
-  if (DP == DP_ && DT == DT_) {                                                              \
-    if (fa_waves && a.prefix_rows)                                                           \
-      launch_fa<DP_, DT_, true>(fa_waves, fa_rpw, fa_deep, grid, stream, a);                 \
-    else if (fa_waves)                                                                       \
-      launch_fa<DP_, DT_, false>(fa_waves, fa_rpw, fa_deep, grid, stream, a);                \
-    else if (use_lds && a.prefix_rows)                                                       \
-      hipLaunchKernelGGL((attn_lds_kernel<DP_, DT_, true>), grid, dim3(256), 0, stream, a);  \
-    else if (use_lds)                                                                        \
-      hipLaunchKernelGGL((attn_lds_kernel<DP_, DT_>), grid, dim3(256), 0, stream, a);        \
-    else if (a.prefix_rows)                                                                  \
-      hipLaunchKernelGGL((attn_kernel<DP_, DT_, true>), grid, dim3(64), 0, stream, a);       \
-    else if (split_keys > 0 && PG_ATTN_SPLIT_WAVES == 1 && D == DP_ && kcap >= 32 && PG_ATTN_WG && DP_ == 256 && \
-             (split_keys == 64 || split_keys % 128 == 0)) {                                  \
-      if (split_keys == 64)                                                                  \
-        hipLaunchKernelGGL((attn_decode_wg_kernel<DP_, DT_, 2>), grid, dim3(128), 0, stream, a); \
-      else                                                                                   \
-        hipLaunchKernelGGL((attn_decode_wg_kernel<DP_, DT_, 4>), grid, dim3(256), 0, stream, a); \
-    } else if (split_keys > 0 && PG_ATTN_SPLIT_WAVES == 1 && D == DP_ && kcap >= 32)         \
-      hipLaunchKernelGGL((attn_decode_kernel<DP_, DT_, true>), grid, dim3(64), 0, stream, a); \
-    else if (split_keys > 0 && PG_ATTN_SPLIT_WAVES == 1)                                     \
-      hipLaunchKernelGGL((attn_decode_kernel<DP_, DT_, false>), grid, dim3(64), 0, stream, a); \
-    else                                                                                     \
-      hipLaunchKernelGGL((attn_kernel<DP_, DT_>), grid, dim3(split_keys > 0 ? 64 * PG_ATTN_SPLIT_WAVES : 64), 0, \
-                         stream, a);                                                         \
-    launched = true;                                                                         \
+// Launch form f at one (DP, DT).  The flash ring is 64-key blocks in two stages (all that fits the 160 KiB of LDS at
+// head_dim 256), 32-key blocks for the 8 x 2 form.  PFX: the prefix-LM instances of pg_attention_prefix, the same forms.
+template <int DP, int DT, bool PFX>
+static void launch_prefill(const AttnForm& f, hipStream_t stream, const AttnArgs& a) {
+  if (f.kind == ATTN_LDS) {
+    hipLaunchKernelGGL((attn_lds_kernel<DP, DT, PFX>), f.grid, dim3(256), 0, stream, a);
+  } else if (f.kind == ATTN_ONE_WAVE) {
+    hipLaunchKernelGGL((attn_kernel<DP, DT, PFX>), f.grid, dim3(64), 0, stream, a);
+  } else if (DP == 256 && f.waves == 8 && f.rpw == 2) {
+    if constexpr (DP == 256)
+      hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 8, 2, 32, 2, PFX>), f.grid, dim3(512), 0, stream, a);
+  } else if (DP == 256 && f.waves == 12) {
+    if constexpr (DP == 256)
+      hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 12, 1, 64, 2, PFX>), f.grid, dim3(768), 0, stream, a);
+  } else if (f.waves == 8) {
+    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 8, 1, 64, 2, PFX>), f.grid, dim3(512), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL((attn_fa_kernel<DP, DT, 4, 1, 64, 2, PFX>), f.grid, dim3(256), 0, stream, a);
   }
+}
+
+template <int DP, int DT>
+static void launch_attn(const AttnForm& f, hipStream_t stream, const AttnArgs& a) {
+  if (f.kind == ATTN_DEC) {
+    hipLaunchKernelGGL((attn_decode_kernel<DP, DT, false>), f.grid, dim3(64), 0, stream, a);
+  } else if (f.kind == ATTN_DEC_FULL) {
+    hipLaunchKernelGGL((attn_decode_kernel<DP, DT, true>), f.grid, dim3(64), 0, stream, a);
+  } else if (f.kind == ATTN_DEC_WG) {
+    if constexpr (DP == 256) {
+      if (f.waves == 2)
+        hipLaunchKernelGGL((attn_decode_wg_kernel<DP, DT, 2>), f.grid, dim3(128), 0, stream, a);
+      else
+        hipLaunchKernelGGL((attn_decode_wg_kernel<DP, DT, 4>), f.grid, dim3(256), 0, stream, a);
+    }
+  } else if (a.prefix_rows) {
+    launch_prefill<DP, DT, true>(f, stream, a);
+  } else {
+    launch_prefill<DP, DT, false>(f, stream, a);
+  }
+}
 
 // V^T rows must be readable up to key 32*ceil(Lkv/32) (pad the row by 32 elements).
 // q/o row for (b, pos, head): q + (b*Lq + pos)*q_rs + head*D.  k for (b, key, kvh): k + b*k_bs + kvh*k_hs + key*k_rs.
@@ -1335,84 +1248,37 @@ static int attention_impl(const void* q, long q_rs, void* o, long o_rs, const vo
     if (split_keys == 0) a.Lkv = 0;
     a.prefix_rows = prefix_rows;                   // picks the PFX instance of whichever prefill form is taken
   }
-  dim3 grid;
-  // prefill with >= 1024 one-wave workgroups: the LDS-staged kernel (64 rows per workgroup share K/V);
-  // needs 16-B aligned V^T rows / batch offsets
-  const long wgs16 = (long)((Lq * G + 15) / 16) * Hkv * B;
+  // 16-B aligned V^T rows / batch offsets (the LDS-staged and flash kernels)
   const bool aligned = vt_ds % 8 == 0 && vt_bs % 8 == 0 && vt_hs % 8 == 0 && k_rs % 8 == 0 && k_bs % 8 == 0 &&
                        k_hs % 8 == 0 && q_rs % 8 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 &&
                        ((uintptr_t)vt & 15) == 0;
-  // LDS-DMA flash kernel for every unmasked prefill; 8 waves (128 rows) per workgroup once that fills the chip
-  int fa_waves = 0, fa_rpw = 1;
-  bool fa_deep = false;
   // (the flash kernel stages by 32-bit offsets from a head's K / V^T base)
   const bool off32 = (unsigned long)(Lkv + 64) * (unsigned long)k_rs * 2ul < (1ul << 32) &&
                      (unsigned long)D * (unsigned long)vt_ds * 2ul < (1ul << 32);
-  if (split_keys == 0 && mask == nullptr && aligned && off32 && lkv_dev == nullptr && PG_ATTN_FA) {
-    // (tests/test_score_gpu.py fa_form restates the wgs / rounds rules below at the default knobs, to know a shape's
-    // workgroup rows and key block: a change of rule or default here is a change there)
-    auto wgs = [&](int rows) { return (long)((Lq * G + rows - 1) / rows) * Hkv * B; };
-    // two 16-row groups per wave (half the LDS fragment reads per flop) when the grid still fills the chip:
-    // 8 waves x 32 rows for head_dim <= 96, else 4 waves x 32 rows (their accumulators need 1 wave / SIMD)
-    auto rounds = [&](int rows) { return (wgs(rows) + 255) / 256; };
-    // head_dim 256, 8 waves x 32 rows on 32-key blocks (twice the flops per LDS fragment read of 16-row waves, two
-    // waves per SIMD at 256 registers): one round costs ~1.55 of an 8 x 16-row round (pt-896 x32 Gemma 5.03 vs
-    // 6.29 ms), so it is taken where its rounds cost less than those of the 8- and 12-wave forms (pt-448 x16 keeps
-    // 12 waves: 3 rounds of 256 rows cost more than 3 of 192)
-    if (PG_FA_W8R2 && DP == 256 && wgs(256) >= 256 &&
-        rounds(256) * 25 < rounds(128) * 16 && (!PG_FA_W12 || rounds(256) * 25 < rounds(192) * 24)) {
-      fa_waves = 8;
-      fa_rpw = 2;
-    } else if (PG_FA_RPW == 2 && DP <= 96 && wgs(256) >= 256) {
-      fa_waves = 8;
-      fa_rpw = 2;
-    } else if (PG_FA_RPW == 2 && wgs(128) >= 256) {
-      fa_waves = 4;
-      fa_rpw = 2;
-    } else {
-      fa_waves = wgs(128) >= 256 ? 8 : 4;
-      // head_dim 256 (166 VGPRs, fits 3 waves / SIMD): 12 waves when the one-workgroup-per-CU rounds cost
-      // less in total (pt-448 x16 Gemma: 688 workgroups in 3 rounds of 192 rows vs 1040 in 5 rounds of 128)
-      if (PG_FA_W12 && DP == 256 && fa_waves == 8 && ((wgs(192) + 255) / 256) * 12 < ((wgs(128) + 255) / 256) * 8) fa_waves = 12;
-      // batch 1 (pt-224: Gemma 2112 stacked rows on one kv head = 33 four-wave workgroups, SigLIP 16 heads x 256
-      // rows = 64): narrower workgroups spread the same rows over 2-4x the CUs; each stages its own K / V^T copy
-      // from L2 (the whole prefix is a few hundred KB)
-      if (PG_FA_SMALL && fa_waves == 4 && wgs(64) < 256) fa_waves = wgs(32) >= 256 ? 2 : 1;
-    }
-    const int rows = 16 * fa_waves * fa_rpw;
-    grid = dim3((Lq * G + rows - 1) / rows, Hkv, B);
-    fa_deep = PG_FA_DEEP && fa_waves == 4 && fa_rpw == 1;
-    if (nsplit > 1) {
-      // prefill key split (caller's workspace: part_o [B][Hkv][nsplit][Lq*G][DT*16] fp32, part_ml [..][2])
-      PG_REQUIRE(nsplit <= PF_MAXS && part_o && part_ml && D % 4 == 0);
-      a.pf_splits = nsplit;
-      grid.x *= nsplit;
-    }
-  } else if (split_keys == 0) {
-    PG_REQUIRE(nsplit <= 1);                       // key splits need the flash kernel's shape conditions
-  }
-  const bool use_lds = fa_waves == 0 && split_keys == 0 && wgs16 >= 1024 && aligned;
-  if (fa_waves) {
-  } else if (use_lds) {
-    grid = dim3((Lq * G + 63) / 64, Hkv, B);
-  } else if (split_keys > 0) {
+  // the LDS-DMA flash kernel for every unmasked prefill
+  const bool flash = split_keys == 0 && mask == nullptr && aligned && off32 && lkv_dev == nullptr;
+  if (split_keys > 0) {
     PG_REQUIRE(Lq * G <= 16 && nsplit % 4 == 0 && part_o && part_ml && split_keys % 32 == 0);
     // a lane reads 8 consecutive keys of a V^T row as one 16-B load (dec_krow)
     PG_REQUIRE(vt_ds % 8 == 0 && vt_bs % 8 == 0 && vt_hs % 8 == 0 && ((uintptr_t)vt & 15) == 0);
-    grid = dim3(1, Hkv * (nsplit / PG_ATTN_SPLIT_WAVES), B);
-  } else {
-    grid = dim3((Lq * G + 15) / 16, Hkv, B);   // one wave (16 query rows) per workgroup: 4x the workgroups
+  } else if (nsplit > 1) {
+    // prefill key split (caller's workspace: part_o [B][Hkv][nsplit][Lq*G][DT*16] fp32, part_ml [..][2]); needs the
+    // flash kernel's shape conditions
+    PG_REQUIRE(flash && nsplit <= PF_MAXS && part_o && part_ml && D % 4 == 0);
+    a.pf_splits = nsplit;
   }
-  bool launched = false;
-  ATTN_DISPATCH(32, 1)
-  ATTN_DISPATCH(32, 2)     // head_dim 24 / 32 (test configs)
-  ATTN_DISPATCH(64, 3)
-  ATTN_DISPATCH(64, 4)
-  ATTN_DISPATCH(96, 5)     // SigLIP head_dim 72
-  ATTN_DISPATCH(96, 6)
-  ATTN_DISPATCH(128, 8)
-  ATTN_DISPATCH(256, 16)   // Gemma head_dim 256
-  if (!launched) return (int)hipErrorInvalidValue;
+  const AttnForm f = attn_form(B, Lq, G, Hkv, D, DP, flash, aligned, split_keys, nsplit, kcap);
+  switch (DT) {                                    // DP = 32 * ceil(DT / 2)
+    case 1: launch_attn<32, 1>(f, stream, a); break;
+    case 2: launch_attn<32, 2>(f, stream, a); break;     // head_dim 24 / 32 (test configs)
+    case 3: launch_attn<64, 3>(f, stream, a); break;
+    case 4: launch_attn<64, 4>(f, stream, a); break;
+    case 5: launch_attn<96, 5>(f, stream, a); break;     // SigLIP head_dim 72
+    case 6: launch_attn<96, 6>(f, stream, a); break;
+    case 8: launch_attn<128, 8>(f, stream, a); break;
+    case 16: launch_attn<256, 16>(f, stream, a); break;  // Gemma head_dim 256
+    default: return (int)hipErrorInvalidValue;           // no kernel at this head_dim
+  }
   PG_LAUNCH_CHECK();
   if (a.pf_splits > 1) {
     const long total = (long)B * Hkv * Lq * G * (D / 4);

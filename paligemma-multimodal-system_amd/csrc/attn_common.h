@@ -112,23 +112,16 @@ static __device__ __forceinline__ u32x4 vmask8(u32x4 v, int n) {
                n >= 6 ? v[2] : (n == 5 ? (v[2] & 0xFFFFu) : 0u), n >= 8 ? v[3] : (n == 7 ? (v[3] & 0xFFFFu) : 0u)};
 }
 
+// A lane's Q fragment of one k-step: dims d0 .. d0 + 7 of the query row at qp, zero past the head's D and for rows past
+// Lq*G (the one-wave, LDS-staged and flash prefill kernels and the guarded decode split).
+static __device__ __forceinline__ bf16x8 attn_q_frag(const bf16_t* qp, int d0, int D, bool rvalid) {
+  return __builtin_bit_cast(bf16x8, ld16_sel(qp + (d0 < D ? d0 : 0), rvalid && d0 < D));
+}
+
 typedef __attribute__((address_space(1))) unsigned long long pg_gu64;
 
-// 16 bytes as two write-through (sc1) 8-B stores: visible to another CU's sc1 loads once the storing wave
-// has drained vmcnt (MI355X guide, inter-workgroup hand-off without a release fence)
-static __device__ __forceinline__ void st16_wt(float* p, f32x4 v) {
-  pg_gu64* d = (pg_gu64*)p;
-  __hip_atomic_store(d, __builtin_bit_cast(unsigned long long, f32x2{v[0], v[1]}), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(d + 1, __builtin_bit_cast(unsigned long long, f32x2{v[2], v[3]}), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-static __device__ __forceinline__ f32x4 ld16_wt(const float* p) {
-  const pg_gu64* s = (const pg_gu64*)p;
-  const f32x2 a = __builtin_bit_cast(f32x2, __hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  const f32x2 b = __builtin_bit_cast(f32x2, __hip_atomic_load(s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  return f32x4{a[0], a[1], b[0], b[1]};
-}
+// 8 bytes by a write-through (sc1) load: sees another CU's sc1 stores once the storing wave has drained vmcnt
+// (MI355X guide, inter-workgroup hand-off without a release fence)
 static __device__ __forceinline__ f32x2 ld8_wt(const float* p) {
   return __builtin_bit_cast(f32x2, __hip_atomic_load((const pg_gu64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
@@ -136,12 +129,12 @@ static __device__ __forceinline__ f32x2 ld8_wt(const float* p) {
 // One decode split, one wave: keys [sp*split_keys, min(Lkv, (sp+1)*split_keys)) of kv head kvh, batch b, for
 // the q rows r < Lq*G (Lq == 1: row r = q head kvh*G + r), written as (O, m, l) partials of split sp of nsplit.
 // S^T = K.Q^T keeps each row's softmax statistics lane-local; O^T = V^T.P^T takes P from the S accumulators
-// (key order permuted identically for V^T).  WT: write-through stores for a consumer inside the same launch.
+// (key order permuted identically for V^T).
 // FULL (head_dim == DP): no lane-dependent selects on loaded values -- rows past Lq*G read row Lq*G-1 (never
 // stored) -- so hipcc has no reason to wait for a load before the next one is issued, and the kv length is
 // read with a vector load (in order with the stream; a scalar load's lgkmcnt wait lands before the first
 // vector load, behind the kernel-argument loads).
-template <int DP, int DT, bool WT, bool FULL = false>
+template <int DP, int DT, bool FULL>
 __device__ __forceinline__ void attn_decode_split(const AttnArgs& a, int b, int kvh, int sp, int nsplit, int lane) {
   constexpr int KS = DP / 32;
   const int c = lane & 15, g = lane >> 4;
@@ -170,7 +163,7 @@ __device__ __forceinline__ void attn_decode_split(const AttnArgs& a, int b, int 
     if constexpr (FULL)
       qf[s] = __builtin_bit_cast(bf16x8, *(const u32x4*)(qp + d0));
     else
-      qf[s] = __builtin_bit_cast(bf16x8, ld16_sel(qp + (d0 < D ? d0 : 0), rvalid && d0 < D));
+      qf[s] = attn_q_frag(qp, d0, D, rvalid);
   }
   const bf16_t* kbase = a.k + (long)b * a.k_bs + (long)kvh * a.k_hs;
   const bf16_t* vbase = a.vt + (long)b * a.vt_bs + (long)kvh * a.vt_hs;
@@ -199,13 +192,8 @@ __device__ __forceinline__ void attn_decode_split(const AttnArgs& a, int b, int 
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       const int d0 = 32 * s + 8 * g;
-      if constexpr (FULL) {
-        kfa[s] = *(const u32x4*)(pa + d0);
-        kfb[s] = *(const u32x4*)(pb + d0);
-      } else {
-        kfa[s] = ld16_sel(pa + (d0 < D ? d0 : 0), d0 < D);
-        kfb[s] = ld16_sel(pb + (d0 < D ? d0 : 0), d0 < D);
-      }
+      kfa[s] = ld16_sel(pa + (d0 < D ? d0 : 0), d0 < D);
+      kfb[s] = ld16_sel(pb + (d0 < D ? d0 : 0), d0 < D);
     }
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
@@ -298,26 +286,18 @@ __device__ __forceinline__ void attn_decode_split(const AttnArgs& a, int b, int 
     }
   }
   // lane holds O^T[d = 16t + 4g + j][q = c]
-  const long base = (((long)b * a.Hkv + kvh) * nsplit + sp) * 16 + c;
 #if PG_ATTN_STAMPS
   asm volatile("" :: "v"(o[0][0]), "v"(o[DT - 1][3]));
   st2 = __builtin_amdgcn_s_memrealtime();
 #endif
   if (!rvalid) return;                       // rows past Lq*G are never merged
+  const long base = (((long)b * a.Hkv + kvh) * nsplit + sp) * 16 + c;
   float* po = a.part_o + base * (DT * 16);
 #pragma unroll
-  for (int t = 0; t < DT; ++t) {
-    if (WT) st16_wt(po + 16 * t + 4 * g, o[t]);
-    else *(f32x4*)(po + 16 * t + 4 * g) = o[t];
-  }
+  for (int t = 0; t < DT; ++t) *(f32x4*)(po + 16 * t + 4 * g) = o[t];
   if (g == 0) {
-    if (WT) {
-      __hip_atomic_store((pg_gu64*)(a.part_ml + base * 2), __builtin_bit_cast(unsigned long long, f32x2{m, l}),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      a.part_ml[base * 2 + 0] = m;
-      a.part_ml[base * 2 + 1] = l;
-    }
+    a.part_ml[base * 2 + 0] = m;
+    a.part_ml[base * 2 + 1] = l;
   }
 #if PG_ATTN_STAMPS
   PG_STAMP(st3);
@@ -349,25 +329,25 @@ __device__ __forceinline__ void attn_decode_block32(const AttnArgs& a, int b, in
   const bf16_t* qp = a.q + ((long)b * a.Lq + pos) * a.q_rs + (long)hq * DP;
 #pragma unroll
   for (int s = 0; s < KS; ++s) qf[s] = __builtin_bit_cast(bf16x8, *(const u32x4*)(qp + 32 * s + 8 * g));
+  // (unused, but hipcc orders the scalar address arithmetic of the wg kernels differently without them:
+  // profiles/attn_refactor_isa.txt)
   const bf16_t* kbase = a.k + (long)b * a.k_bs + (long)kvh * a.k_hs;
   const bf16_t* vbase = a.vt + (long)b * a.vt_bs + (long)kvh * a.vt_hs;
+  (void)kbase;
+  (void)vbase;
   // a block past the cache reads the last block (never used: all its keys are masked)
   const int kl = min(kb, a.kcap - 32);
   u32x4 kfa[KS], kfb[KS];
   u32x4 vr[DT];
-  {
-    (void)kbase;
-    (void)vbase;
-    const bf16_t* kdb = a.kd + ((long)b * a.Hkv + kvh) * a.kcap * DP;
-    const bf16_t* vdb = a.vd + ((long)b * a.Hkv + kvh) * a.kcap * DP;
+  const bf16_t* kdb = a.kd + ((long)b * a.Hkv + kvh) * a.kcap * DP;
+  const bf16_t* vdb = a.vd + ((long)b * a.Hkv + kvh) * a.kcap * DP;
 #pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      kfa[s] = *(const u32x4*)(kdb + dec_kfrag(kl, 0, s, c, g, DP));
-      kfb[s] = *(const u32x4*)(kdb + dec_kfrag(kl, 1, s, c, g, DP));
-    }
-#pragma unroll
-    for (int t = 0; t < DT; ++t) vr[t] = *(const u32x4*)(vdb + dec_vfrag(kl, t, c, g, DP));
+  for (int s = 0; s < KS; ++s) {
+    kfa[s] = *(const u32x4*)(kdb + dec_kfrag(kl, 0, s, c, g, DP));
+    kfb[s] = *(const u32x4*)(kdb + dec_kfrag(kl, 1, s, c, g, DP));
   }
+#pragma unroll
+  for (int t = 0; t < DT; ++t) vr[t] = *(const u32x4*)(vdb + dec_vfrag(kl, t, c, g, DP));
   // every load of the block is issued before its first use (one memory round trip)
   __builtin_amdgcn_sched_barrier(0);
   const int Lkv = __builtin_amdgcn_readfirstlane(lkv_raw) + a.Lkv;

@@ -150,7 +150,12 @@ def census_ok(o, D, lens) -> bool:
 def needle_gain(D) -> float:
     """c of q = c k[needle]: the needle's logit is c sqrt(D), the others' c N(0, 1); the mean weight off the needle is
     about L exp(c^2 / 2 - c sqrt(D)).  32 / sqrt(D) puts the needle at logit 32 (c = 2 at D = 256); sqrt(D) is the best
-    any c does, and is taken for the small head_dims (D < 32).  Rounded to a multiple of 1/8: c * (+-1) is bf16-exact."""
+    any c does, and is taken for the small head_dims (D < 32).  Rounded to a multiple of 1/8: c * (+-1) is bf16-exact.
+    D < 24 (head_dim 16): among a few hundred rows of random signs some key agrees with a needle in all dims but one
+    (D 2^-D per pair), and its logit is only 2 c / sqrt(D) below the needle's whatever the spread of the others, so
+    there the gain is 4 sqrt(D): that key sits 8 below, the needle at logit 4 D = 64."""
+    if D < 24:
+        return round(4.0 * math.sqrt(D) * 8) / 8
     return round(min(32.0 / math.sqrt(D), math.sqrt(D)) * 8) / 8
 
 

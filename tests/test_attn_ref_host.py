@@ -56,6 +56,23 @@ def test_emulation_within_half_the_bound(name, D):
     assert worst <= R.C / 2, worst
 
 
+@pytest.mark.parametrize("D", (16, 40, 88))
+def test_emulation_within_half_the_bound_at_the_other_head_dims(D):
+    """C was measured at head_dims 32, 72 and 256.  test_attn_structured_gpu.test_every_head_dim_instance also runs
+    needle and ramp at 16, 40 and 88 (the other (DP, DT) kernel instances) under the same C, at L = 70: the emulation
+    stays within C / 2 there too, at that length and over several key blocks."""
+    worst = 0.0
+    for name in ("needle", "ramp_up", "ramp_down"):
+        for L in (70, 264):
+            q, k, v = _inputs(name, D, L)
+            o, budget = R.ref(q, k, v, D ** -0.5, lens=[L])
+            for block in (32, 64):
+                e = R.emulate(q, k[:, :, :L], v[:, :, :L], D ** -0.5, block)
+                worst = max(worst, R.worst_ratio(e, o, budget))
+    print(f"emulation needle / ramp D={D}: worst |o - ref| / budget = {worst * 256:.3f} * 2^-8")
+    assert worst <= R.C / 2, worst
+
+
 def test_the_bound_is_twice_the_measured_worst_rounded_up_to_a_power_of_two():
     assert R.C == 2.0 ** math.ceil(math.log2(2 * R.EMU_WORST))
 

@@ -5,9 +5,9 @@ Bounds (attn_ref): census |o - count_d / L| <= 2^-7 count_d / L; everything else
 element with budget = softmax @ |v| and C = 2^-6 from the CPU emulation.  Each case prints its worst ratio (in units of
 the bound's own scale: count_d / L for census, budget otherwise).
 
-The form a shape reaches is decided by attention_impl (csrc/attn.hip) with the build's defaults PG_FA_RPW 1, PG_FA_W12 1,
-PG_FA_W8R2 1, PG_FA_SMALL 0, PG_FA_DEEP 0; the arithmetic stands beside each shape.  Shapes are (B, L, nh, nkv, hd),
-rows = L nh / nkv stacked query rows per kv head, wgs(r) = ceil(rows / r) nkv B, rounds(r) = ceil(wgs(r) / 256).
+The form a shape reaches is decided by attn_form (csrc/attn.hip); the arithmetic stands beside each shape.  Shapes are
+(B, L, nh, nkv, hd), rows = L nh / nkv stacked query rows per kv head, wgs(r) = ceil(rows / r) nkv B, rounds(r) =
+ceil(wgs(r) / 256).
 """
 import pytest
 import torch
@@ -133,7 +133,7 @@ def _split_first_key(n, nks):
     return (nblk - 1) // per * per * 64
 
 
-def _prefill(shape, ragged):
+def _prefill(shape, ragged, names=None):
     from pghip import ops
     B, L, nh, nkv, hd, nks, masked = shape
     Smax = _smax(L)
@@ -151,7 +151,7 @@ def _prefill(shape, ragged):
                   part_ml=torch.full((nml,), float("nan"), device="cuda"))
     if masked:
         kw.update(mask=torch.zeros(B, L, L, device="cuda"), mask_bs=L * L, mask_rs=L)
-    for name, q, k, v, ref, unit, c in _cases(B, nh, nkv, L, hd, Smax, lens, spikes):
+    for name, q, k, v, ref, unit, c in _cases(B, nh, nkv, L, hd, Smax, lens, spikes, names=names):
         qf, kc, vtc = _layout(q, k, v)
         o = torch.full((B * L, nh * hd), float("nan"), dtype=BF, device="cuda")
         args = (qf, nh * hd, o, nh * hd, kc, Smax * kvd, hd, kvd, vtc, kvd * Smax, hd * Smax, Smax)
@@ -202,27 +202,27 @@ def _split_edges(lens, ranges):
     return sorted(e for e in edges if 0 <= e < top)
 
 
-def _decode_split(shape, ragged):
+def _decode_split(shape, ragged, split_keys=SPLIT_KEYS, names=None):
     from pghip import ops
     B, L, nh, nkv, hd, Smax = shape
     kvd = nkv * hd
     lens = _decode_lens(B, Smax) if ragged else [L] * B
-    ranges = [(s * sk, (s + 1) * sk) for sk in SPLIT_KEYS for s in range(-(-Smax // sk))]
+    ranges = [(s * sk, (s + 1) * sk) for sk in split_keys for s in range(-(-Smax // sk))]
     fills = R.edge_fills(_split_edges(lens, ranges), B, nkv, lens)
     spikes = {"last": [_last_block_key(n) for n in lens]}
-    for sk in SPLIT_KEYS:                             # the first block of the last non-empty split of sk keys
+    for sk in split_keys:                             # the first block of the last non-empty split of sk keys
         sp = [(n - 1) // sk * sk for n in lens]
         if sp not in spikes.values():
             spikes[f"first{sk}"] = sp
     tag = f"decode_split{'_rows' if ragged else ''} {shape}"
     dt = (hd + 15) // 16 * 16
     packed = hd % 32 == 0
-    for name, q, k, v, ref, unit, c in _cases(B, nh, nkv, 1, hd, Smax, lens, spikes, fills):
+    for name, q, k, v, ref, unit, c in _cases(B, nh, nkv, 1, hd, Smax, lens, spikes, fills, names=names):
         qf, kc, vtc = _layout(q, k, v)
         kd, vd = ops.decode_cache_pack(kc, vtc, nkv) if packed else (None, None)
         args = (qf, nh * hd, None, nh * hd, kc, Smax * kvd, hd, kvd, vtc, kvd * Smax, hd * Smax, Smax)
         worst = 0.0
-        for sk in SPLIT_KEYS:
+        for sk in split_keys:
             ns = ((Smax + sk - 1) // sk + 3) // 4 * 4
             po = torch.full((B * nkv * ns * 16 * dt,), float("nan"), device="cuda")
             pml = torch.full((B * nkv * ns * 16 * 2,), float("nan"), device="cuda")
@@ -245,6 +245,27 @@ def test_decode_splits_and_combine(shape, ragged):
     """pg_attention / pg_attention_rows in split mode + pg_attn_combine over 32- to 256-key splits, with and without the
     decode-order copies: every split's first and last key is some (row, kv head)'s needle."""
     _decode_split(shape, ragged)
+
+
+# ------------------------------------------------------------------- every (DP, DT) instance the launcher selects
+# head_dim -> (DP, DT) = (32 ceil(hd / 32), ceil(hd / 16)), the eight pairs of attention_impl's switch (csrc/attn.hip)
+HEAD_DIMS = {16: (32, 1), 24: (32, 2), 40: (64, 3), 64: (64, 4), 72: (96, 5), 88: (96, 6), 128: (128, 8),
+             256: (256, 16)}
+
+
+@pytest.mark.parametrize("hd", list(HEAD_DIMS))
+def test_every_head_dim_instance(hd):
+    """Needle and ramps through each (DP, DT) instance: B 2, L 70, nh 4, nkv 2 is rows 140, wgs(128) = 2 * 2 * 2 = 8
+    < 256 -> the 4-wave flash form; under an all-zero additive mask wgs16 = 9 * 2 * 2 = 36 < 1024 -> the one-wave
+    kernel; 32-key decode splits with kcap = 0 (attn_decode_kernel<false>) and with kcap = Smax, which is
+    attn_decode_kernel<true> where head_dim == DP (64, 128, 256) and the guarded kernel with its first block
+    prefetched elsewhere.  The bound is C: tests/test_attn_ref_host.py holds the emulation to C / 2 at 16, 40 and 88."""
+    assert HEAD_DIMS[hd] == ((hd + 31) // 32 * 32, (hd + 15) // 16)
+    B, L, nh, nkv = 2, 70, 4, 2
+    names = ("needle", "ramp")
+    _prefill((B, L, nh, nkv, hd, 0, False), ragged=False, names=names)
+    _prefill((B, L, nh, nkv, hd, 0, True), ragged=False, names=names)
+    _decode_split((B, L, nh, nkv, hd, _smax(L)), ragged=False, split_keys=(32,), names=names)
 
 
 # ---------------------------------------------------------------------------------------------------- fused decode

@@ -70,8 +70,8 @@ def _attn_ref_prefix(q, k, v, scale, n, prefix):
 
 
 def fa_form(B, L, nh, nkv, hd):
-    """(query rows per workgroup, keys per block) of the flash form attention_impl picks for an unmasked prefill (its
-    wgs / rounds rules restated; the tuning knobs at their defaults)."""
+    """(query rows per workgroup, keys per block) of the flash form attn_form (csrc/attn.hip) picks for an unmasked
+    prefill (its wgs / rounds rules restated)."""
     G, DP = nh // nkv, (hd + 31) // 32 * 32
     wgs = lambda rows: -(-L * G // rows) * nkv * B       # noqa: E731
     rounds = lambda rows: -(-wgs(rows) // 256)           # noqa: E731
