@@ -387,6 +387,29 @@ int pg_kv_beam_gather(void* k, void* vt, void* kd, void* vd, int layers, int row
                       const int* parent, const int* base, const int* len_dev, int len_rows, int len_base,
                       void* scratch, int S_scr, hipStream_t stream);
 
+/* (added under ABI 13; the version stays 13, nothing existing changed)  Constrained decoding: a DFA over token classes
+ * restricts what the sampler may pick (pghip/grammar.py TokenDFA).  cls int16 [V] is the class of every token id
+ * (class 0: never allowed), trans int16 [S][C] the next state or -1, so token t is allowed in state s iff
+ * trans[s*C + cls[t]] >= 0.  state int32 [B] holds one DFA state per row on the device; a negative state, or one >= S,
+ * is "free": the row is not constrained.  For every row b with s = state[b] in [0, S) and every t in [0, V) that s does
+ * not allow (a class outside [0, C) counts as class 0), logits[b*ld + t] = -inf.  The logits are never read: every
+ * other word -- NaN payloads, -inf, the padding columns [V, ld) -- keeps its exact bits, and a free row is not touched
+ * at all.  logits fp32, row stride ld floats (>= V when B > 1), any 4-byte alignment: four consecutive dead tokens
+ * are one 16-byte store where the address allows it, single stores otherwise.  A row is split over 64 workgroups, each
+ * of which turns the state's trans row into a C-bit bitmap in LDS and streams cls (16-byte loads when cls is 16-B
+ * aligned).  The state is read on the device, so the launch has a fixed grid and is graph-capturable.  Null pointers,
+ * B outside [1, 1024], V < 1, ld < V with B > 1, S outside [1, 32767] and C outside [2, 4096] return
+ * hipErrorInvalidValue before any HIP call. */
+int pg_dfa_mask(float* logits, long ld, int B, int V, const int16_t* cls, const int16_t* trans, int S, int C,
+                const int* state, hipStream_t stream);
+/* (added under ABI 13)  The DFA step after the sampler: for every row b with s = state[b] in [0, S), n = trans[s*C +
+ * cls[ids[b]]]; n >= 0 becomes state[b]; n < 0, and an id outside [0, V), leave state[b] and write *err = 1 (plain
+ * vector stores; the caller clears it).  That happens only when the sampler was handed a row whose allowed tokens were
+ * all NaN, so that pg_argmax fell back to token 0.  A free row stays free and never sets *err.  One workgroup, one
+ * thread per row; ids int64 [B] as the samplers write them.  Rejections as pg_dfa_mask (no ld here). */
+int pg_dfa_advance(int* state, const int64_t* ids, int B, int V, const int16_t* cls, const int16_t* trans, int S, int C,
+                   int* err, hipStream_t stream);
+
 /* vocabulary-parallel greedy for tensor parallelism: local (max, first global index) pairs [B][2] of a
  * vocab shard starting at vocab_offset; after an all-gather, pg_argmax_merge takes the global winner
  * (lowest index on ties, as torch.argmax) and advances the decode state like pg_argmax. */

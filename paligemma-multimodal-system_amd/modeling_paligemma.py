@@ -211,8 +211,12 @@ class PaliGemmaForConditionalGeneration(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, pixel_values, attention_mask=None, max_new_tokens: int = 100,
                  do_sample: bool = False, temperature: float = 0.8, top_p: float = 0.9, uniforms=None,
-                 stop_token: Optional[int] = 1):
+                 stop_token: Optional[int] = 1, grammar=None, grammar_start=None):
         """The token loop of inference.py:45-82 on the engine (vision once, hipGraph-replayed decode steps).
+
+        grammar (pghip.grammar.TokenDFA, e.g. PaliGemmaProcessor.detect_grammar / choices_grammar): constrained
+        decoding -- every token is picked among those the grammar allows, on the device; grammar_start: the start
+        state, or one per row with -1 for an unconstrained row (PaliGemmaEngine.generate).
 
         Several prompts of different lengths go in one call as a right-padded batch (PaliGemmaProcessor.batch):
         input_ids padded with pad_token_id, attention_mask ones over each row's own tokens and zeros after them.
@@ -223,4 +227,5 @@ class PaliGemmaForConditionalGeneration(nn.Module):
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         return eng.generate(input_ids, pixel_values, attention_mask, max_new_tokens, do_sample=do_sample,
-                            temperature=temperature, top_p=top_p, uniforms=uniforms, stop_token=stop_token)
+                            temperature=temperature, top_p=top_p, uniforms=uniforms, stop_token=stop_token,
+                            grammar=grammar, grammar_start=grammar_start)

@@ -60,6 +60,8 @@ SIGNATURES = {
     "pg_token_logprob": [vp, i64, i32, i32, vp, vp, vp, vp, vp],
     "pg_beam_select": [vp, i64, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
     "pg_kv_beam_gather": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp],
+    "pg_dfa_mask": [vp, i64, i32, i32, vp, vp, i32, i32, vp, vp],
+    "pg_dfa_advance": [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp],
     "pg_argmax_embed": [vp, i64, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, i64, i64, f32, f32, vp,
                         vp],
     "pg_argmax_pairs": [vp, i64, i32, i32, i32, vp, vp, vp],

@@ -732,7 +732,9 @@ class PaliGemmaEngine:
 
     def decode_step(self, st: dict, cache: KVStore, feats: Optional[torch.Tensor], sampler: dict):
         """One token for B rows: embed(ids) -> 18 layers -> lm_head -> argmax/top-p (advances the state).  The layers
-        run in the form _decode_route picks for B, on the buffers and splits of one _decode_ws record."""
+        run in the form _decode_route picks for B, on the buffers and splits of one _decode_ws record.  Returns the
+        step's logits; with a grammar in the sampler they are the masked ones (-inf where a row's DFA state did not
+        allow the token: sample() masks the buffer in place)."""
         w = self.w
         B = st["ids"].numel()
         ws = self._decode_ws(B, cache)
@@ -1071,9 +1073,14 @@ class PaliGemmaEngine:
     def sample(self, logits: torch.Tensor, st: dict, sampler: dict, advance: bool,
                feats: Optional[torch.Tensor] = None):
         """Next ids from logits [B][V] (greedy or top-p); advance=True also moves pos / kv_len on.  A chained
-        state (decode_state) also gets the next step's input rows: pass the request's image features."""
+        state (decode_state) also gets the next step's input rows: pass the request's image features.
+        sampler["grammar"] (grammar_state): pg_dfa_mask on the logits, in place, before the sampler that would have run
+        anyway, and pg_dfa_advance on the ids it wrote -- two small launches, nothing leaves the device."""
         if sampler.get("beam") is not None:
             return self._beam_sample(logits, st, sampler["beam"], advance)
+        gr = sampler.get("grammar")
+        if gr is not None:      # constrained rows: -inf over what their DFA state does not allow, then the same sampler
+            ops.dfa_mask(logits, gr["cls"], gr["trans"], gr["state"])
         kw = dict(hist=st["hist"], step=st["step"])
         if advance:     # (per-row lengths: pos[b] is the row's length too, and the samplers leave a null kv_len alone)
             kw.update(pos=st["pos"], kv_len=None if st.get("ragged") else st["kv_len"])
@@ -1087,6 +1094,8 @@ class PaliGemmaEngine:
                             top_p=sampler["top_p"], **kw)
         else:
             ops.argmax(logits, st["ids"], st["ws"], **kw)
+        if gr is not None:      # ... and the states follow the tokens picked
+            ops.dfa_advance(gr["state"], st["ids"], gr["cls"], gr["trans"], gr["err"])
 
     def _beam_sample(self, logits: torch.Tensor, st: dict, bm: dict, advance: bool):
         """The beam sampler: pg_beam_select on the step's logits (ids, parents, scores, finished flags, both histories
@@ -1232,7 +1241,8 @@ class PaliGemmaEngine:
 
     def generate(self, input_ids, pixel_values, attention_mask, max_new_tokens: int, do_sample=False,
                  temperature=0.8, top_p=0.9, uniforms=None, stop_token: Optional[int] = 1, use_graph=True,
-                 check_every: Optional[int] = None, pad_token: int = 0, return_list: bool = False):
+                 check_every: Optional[int] = None, pad_token: int = 0, return_list: bool = False,
+                 grammar=None, grammar_start=None):
         """test_inference's loop (inference.py:45-82) for B >= 1 rows.
 
         B = 1: ids [1][n], stopping after EOS like the reference.  B > 1 (the reference asserts B = 1,
@@ -1240,13 +1250,28 @@ class PaliGemmaEngine:
         `stop_token` (checked every `check_every` steps, default 8, one host sync each) or max_new_tokens;
         a row's tokens after its EOS are replaced by `pad_token` in the [B][n] result, or dropped when
         return_list=True (a list of per-row id lists, each ending at its EOS).  Rows of different prompt lengths:
-        a right-padded attention_mask (prefill_request); each row then generates what it generates alone at B = 1."""
+        a right-padded attention_mask (prefill_request); each row then generates what it generates alone at B = 1.
+
+        grammar (a pghip.grammar.TokenDFA): constrained decoding.  Every token, the first included, is picked among
+        those the row's DFA state allows -- the others' logits are set to -inf on the device before the greedy or
+        top-p sampler runs (pg_dfa_mask), and the state follows the pick (pg_dfa_advance); the step stays one graph.
+        grammar_start: the start state, an int or one per row; -1 leaves a row unconstrained (it generates what it
+        generates without a grammar); default: the grammar's single start state.  A grammar whose cls does not cover
+        the vocabulary, a start state outside {-1} U [0, S) and a start list of the wrong length raise ValueError
+        before anything is launched; tp > 1 raises NotImplementedError.  Should a constrained row's allowed logits all
+        be NaN, the sampler's fallback token breaks the grammar: RuntimeError after the loop."""
         B = input_ids.shape[0]
         if check_every is None:
             check_every = 1 if B == 1 else 8
+        starts = self.grammar_args(grammar, grammar_start, B, self.w.vocab)     # host checks, before any launch
+        if grammar is not None and self.tp > 1:
+            raise NotImplementedError("constrained decoding (grammar=) is not supported under tensor parallelism "
+                                      "(tp > 1)")
         cache, feats, logits, nxt = self.prefill_request(input_ids, pixel_values, attention_mask, max_new_tokens)
         sampler = dict(do_sample=do_sample, temperature=temperature, top_p=top_p)
         st = self.decode_state(B, cache, nxt, max_new_tokens, sampler=sampler)
+        if grammar is not None:
+            sampler["grammar"] = self.grammar_state(grammar, starts)
         if do_sample:
             if uniforms is None:
                 uniforms = torch.rand(max_new_tokens + 1, B)
@@ -1276,6 +1301,9 @@ class PaliGemmaEngine:
             n += 1
         hist = st["hist"][:n].t().contiguous().cpu()
         self.check_numerics()
+        if grammar is not None and int(sampler["grammar"]["err"].item()):
+            raise RuntimeError("constrained decoding: a sampled token was not allowed by its row's grammar state (the "
+                               "row's allowed logits were all NaN); the generated tokens are invalid")
         if hasattr(self.comm, "check"):
             self.comm.check()              # an xGMI exchange that timed out leaves meaningless sums: raise
         if stop_token is None:
@@ -1291,6 +1319,38 @@ class PaliGemmaEngine:
         for b, r in enumerate(rows):
             out[b, : len(r)] = torch.tensor(r, dtype=torch.int64)
         return out
+
+    @staticmethod
+    def grammar_args(grammar, grammar_start, B: int, vocab: int):
+        """Host checks of generate's grammar arguments (ValueError before anything is launched); returns the B start
+        states, or None without a grammar."""
+        if grammar is None:
+            if grammar_start is not None:
+                raise ValueError("grammar_start given without a grammar")
+            return None
+        if len(grammar.cls) != vocab:
+            raise ValueError(f"the grammar classifies {len(grammar.cls)} token ids, the model's vocabulary has {vocab}")
+        if grammar_start is None:
+            starts = [grammar.start] * B
+        elif isinstance(grammar_start, (list, tuple)):
+            starts = list(grammar_start)
+            if len(starts) != B:
+                raise ValueError(f"grammar_start lists {len(starts)} start states for {B} rows")
+        else:
+            starts = [grammar_start] * B
+        for s in starts:
+            if isinstance(s, bool) or not isinstance(s, int) or not -1 <= s < grammar.S:
+                raise ValueError(f"grammar_start {s!r}: a start state is -1 (a free row) or in [0, {grammar.S})")
+        return starts
+
+    def grammar_state(self, grammar, starts) -> dict:
+        """What sample() needs of a grammar, on the device: the two tables (uploaded once per call), one state word per
+        row and the error word."""
+        dev = self.device
+        return dict(cls=torch.from_numpy(grammar.cls).to(dev).contiguous(),
+                    trans=torch.from_numpy(grammar.trans).to(dev).contiguous(),
+                    state=torch.tensor(starts, dtype=torch.int32, device=dev),
+                    err=torch.zeros(1, dtype=torch.int32, device=dev))
 
     @staticmethod
     def beam_args(num_beams, num_return_sequences, max_new_tokens, vocab: int, length_penalty=1.0):
@@ -1454,6 +1514,9 @@ class PaliGemmaEngine:
                      (cache.vt[..., lo:hi], cache.vt[..., lo:hi].clone()),
                      (kv5(cache.kd)[:, :, :, lo:hi], kv5(cache.kd)[:, :, :, lo:hi].clone()),
                      (kv5(cache.vd)[:, :, :, lo:hi], kv5(cache.vd)[:, :, :, lo:hi].clone())]
+        gr = sampler.get("grammar") if sampler is not None else None
+        if gr is not None:      # the DFA states the warm-up step moves on: the captured loop must not start a token ahead
+            gsnap = {k: gr[k].clone() for k in ("state", "err")}
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         try:
@@ -1472,6 +1535,9 @@ class PaliGemmaEngine:
                     bm[k].copy_(v)
                 for dst, src in csnap:
                     dst.copy_(src)
+            if gr is not None:
+                for k, v in gsnap.items():
+                    gr[k].copy_(v)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self.decode_step(st, cache, feats, sampler)

@@ -621,6 +621,56 @@ def kv_beam_gather(k, vt, kd, vd, parent, base, len_dev, scratch, *, kv_heads: i
               _p(parent), _p(base), _p(len_dev), int(bool(len_rows)), int(len_base), _p(scratch), S_scr, _s())
 
 
+DFA_MAX_STATES = 32767      # states a token DFA may have (int16 next states; csrc/grammar.hip DM_MAX_S)
+DFA_MAX_CLASSES = 4096      # ... and token classes (the allowed bitmap is 512 bytes of LDS; DM_MAX_C)
+DFA_MAX_ROWS = 1024         # rows per pg_dfa_mask / pg_dfa_advance call (DM_MAX_B)
+
+
+def _chk_dfa(name: str, cls, trans, state, B: int, V: int):
+    """Host checks shared by dfa_mask / dfa_advance; returns (S, C)."""
+    _chk(cls, torch.int16, "cls")
+    _chk(trans, torch.int16, "trans")
+    _chk(state, torch.int32, "state")
+    if trans.dim() != 2 or not trans.is_contiguous() or not cls.is_contiguous() or not state.is_contiguous():
+        raise ValueError(f"pghip.{name}: trans must be a contiguous [S][C], cls and state contiguous")
+    S, C = trans.shape
+    if cls.numel() != V or state.numel() != B:
+        raise ValueError(f"pghip.{name}: cls holds {cls.numel()} classes for V = {V}, state {state.numel()} rows for "
+                         f"B = {B}")
+    if not 1 <= S <= DFA_MAX_STATES or not 2 <= C <= DFA_MAX_CLASSES or not 1 <= B <= DFA_MAX_ROWS:
+        raise ValueError(f"pghip.{name}: S = {S} (1..{DFA_MAX_STATES}), C = {C} (2..{DFA_MAX_CLASSES}), B = {B} "
+                         f"(1..{DFA_MAX_ROWS})")
+    return S, C
+
+
+def dfa_mask(logits, cls, trans, state):
+    """Constrained decoding, before the sampler (pg_dfa_mask): logits fp32 [B][V] (unit column stride, any row stride
+    >= V) get -inf wherever row b's DFA state does not allow the token, trans[state[b]][cls[t]] < 0; every other word
+    keeps its bits, and a row whose state is negative (free) or >= S is not touched.  cls int16 [V], trans int16
+    [S][C], state int32 [B], all on the device (pghip/grammar.py TokenDFA)."""
+    _chk(logits, torch.float32, "logits")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("pghip.dfa_mask: logits must be [B][V] with unit column stride")
+    B, V = logits.shape
+    if B > 1 and logits.stride(0) < V:
+        raise ValueError(f"pghip.dfa_mask: row stride {logits.stride(0)} below V = {V}")
+    S, C = _chk_dfa("dfa_mask", cls, trans, state, B, V)
+    _lib.call("pg_dfa_mask", _p(logits), max(logits.stride(0), V), B, V, _p(cls), _p(trans), S, C, _p(state), _s())
+
+
+def dfa_advance(state, ids, cls, trans, err):
+    """Constrained decoding, after the sampler (pg_dfa_advance): state[b] = trans[state[b]][cls[ids[b]]] for every
+    constrained row; a token its state does not allow (or an id outside [0, V)) leaves the state and sets err[0] = 1.
+    state int32 [B] in place, ids int64 [B], err int32 [1]."""
+    _chk(ids, torch.int64, "ids")
+    _chk(err, torch.int32, "err")
+    B = ids.numel()
+    if not ids.is_contiguous() or err.numel() < 1:
+        raise ValueError("pghip.dfa_advance: ids must be contiguous and err hold one word")
+    S, C = _chk_dfa("dfa_advance", cls, trans, state, B, cls.numel())
+    _lib.call("pg_dfa_advance", _p(state), _p(ids), B, cls.numel(), _p(cls), _p(trans), S, C, _p(err), _s())
+
+
 def argmax_embed(logits, out_ids, workspace, embed, feat, n_feat, res, *, image_id, pad_id, img_scale, normalizer,
                  hist=None, step=None, pos=None, kv_len=None):
     """argmax + the next step's input rows res[b] = embed_merge(winner_b) (one launch fewer per decode step)."""

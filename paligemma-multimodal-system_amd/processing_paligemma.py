@@ -84,6 +84,101 @@ class PaliGemmaProcessor:
         toks = self.tokenizer(s, return_tensors="pt", truncation=truncation, padding=padding)
         return {"pixel_values": pixel_values, **toks}
 
+    # ------------------------------------------------------------------ constrained decoding (pghip/grammar.py)
+    def _ids(self, text: str, known: bool = False) -> List[int]:
+        ids = list(self.tokenizer(text, add_special_tokens=False)["input_ids"])
+        unk = getattr(self.tokenizer, "unk_token_id", None)
+        if known and unk is not None and unk in ids:
+            raise ValueError(f"{text!r} holds a word the tokenizer does not know (<unk>): it cannot be generated")
+        return ids
+
+    def detect_grammar(self, labels: Sequence[str], vocab: Optional[int] = None):
+        """The TokenDFA of a ``detect a ; b`` answer: ``<loc><loc><loc><loc> label`` boxes separated by `` ;``, then
+        ``<eos>``, or ``<eos>`` alone (TokenDFA.detect).  Pass it to ``generate(..., grammar=...)``; parse_detections
+        reads the result.  vocab: the model's vocabulary size (config.vocab_size) when it exceeds the tokenizer's
+        length, which is the default; ids past the tokenizer are never allowed.
+
+        Limitation: a label is accepted only in the tokenisation the tokenizer gives for ``" " + label``
+        (add_special_tokens=False), not in every token sequence that decodes to the same text."""
+        from pghip.grammar import TokenDFA
+        labels = [str(lb).strip() for lb in labels]
+        if not labels or any(not lb for lb in labels):
+            raise ValueError(f"detect_grammar: needs non-empty labels, got {labels!r}")
+        tok = self.tokenizer
+        loc_ids = tok.convert_tokens_to_ids([f"<loc{i:04d}>" for i in range(1024)])
+        if tok.eos_token_id is None or any(i is None or i == tok.unk_token_id for i in loc_ids):
+            raise ValueError("detect_grammar: the tokenizer lacks <eos> or the <loc> tokens")
+        vocab = len(tok) if vocab is None else int(vocab)
+        # (a model whose vocabulary stops inside the <loc> range can only ever emit the ids below it)
+        dfa = TokenDFA.detect([i for i in loc_ids if i < vocab], [self._ids(" " + lb, True) for lb in labels],
+                              self._ids(" ;"), tok.eos_token_id, vocab)
+        dfa.meta.update(labels=labels, loc_ids=loc_ids)         # loc_ids[n] is <locNNNN>, for parse_detections
+        self._detect_dfa = dfa
+        return dfa
+
+    def choices_grammar(self, choices: Sequence[str], vocab: Optional[int] = None):
+        """The TokenDFA of a closed answer set: one of `choices`, tokenised as the tokenizer gives them, then ``<eos>``
+        (TokenDFA.from_choices; vocab as detect_grammar; the same tokenisation limitation)."""
+        from pghip.grammar import TokenDFA
+        choices = [str(c) for c in choices]
+        if not choices or any(not c.strip() for c in choices):
+            raise ValueError(f"choices_grammar: needs non-empty choices, got {choices!r}")
+        tok = self.tokenizer
+        if tok.eos_token_id is None:
+            raise ValueError("choices_grammar: the tokenizer has no <eos>")
+        dfa = TokenDFA.from_choices([self._ids(c, True) for c in choices], tok.eos_token_id,
+                                    len(tok) if vocab is None else int(vocab))
+        dfa.meta["choices"] = choices
+        return dfa
+
+    def parse_detections(self, ids_or_text, height: int, width: int, grammar=None) -> List[dict]:
+        """A constrained ``detect`` answer as ``[{"label": str, "box": (y_min, x_min, y_max, x_max)}]`` in pixels of a
+        height x width image: ``<locNNNN>`` is NNNN / 1024 of the height (a box's first and third) or of the width
+        (second and fourth).  ids_or_text: the generated ids, ending at ``<eos>`` (a tensor, or a list), or the decoded
+        text (tokenised again; its ``<eos>`` may be missing).  grammar: the detect grammar the answer was generated
+        under, by default the last one detect_grammar built.  A sequence that grammar does not accept (TokenDFA.accepts)
+        raises ValueError naming the position of the first token it refuses."""
+        dfa = grammar if grammar is not None else getattr(self, "_detect_dfa", None)
+        if dfa is None or dfa.meta.get("kind") != "detect":
+            raise ValueError("parse_detections: needs a detect grammar (call detect_grammar first, or pass grammar=)")
+        m = dfa.meta
+        if isinstance(ids_or_text, str):
+            ids = self._ids(ids_or_text)
+            if not ids or ids[-1] != m["eos"]:
+                ids.append(m["eos"])
+        else:
+            ids = [int(t) for t in (ids_or_text.reshape(-1).tolist() if hasattr(ids_or_text, "reshape")
+                                    else ids_or_text)]
+        if not dfa.accepts(ids):
+            _, n = dfa.walk(ids)
+            what = f"token {ids[n]} at position {n}" if n < len(ids) else f"its end at position {n} (no <eos>)"
+            raise ValueError(f"parse_detections: not a detect answer for labels {m.get('labels')}: {what} is not "
+                             "allowed by the grammar")
+        loc = {t: i for i, t in enumerate(m["loc_ids"])}
+        names = {tuple(q): lb for q, lb in zip(m.get("label_seqs", ()), m.get("labels", ()))}
+        out, s, coords, label_from = [], dfa.start, [], None
+
+        def close(upto: int):
+            y0, x0, y1, x1 = coords
+            text = names.get(tuple(ids[label_from:upto]))       # the label as it was given, not a re-decoded spelling
+            if text is None:
+                text = self.tokenizer.decode(ids[label_from:upto], skip_special_tokens=True).strip()
+            out.append({"label": text, "box": (y0 / 1024 * height, x0 / 1024 * width, y1 / 1024 * height,
+                                               x1 / 1024 * width)})
+
+        for i, t in enumerate(ids):
+            s = dfa.step(s, t)
+            if t in loc and label_from is None:
+                coords.append(loc[t])
+            if s == m["label_state"]:
+                label_from = i + 1
+            elif label_from is not None and (s == m["box_state"] or s in dfa.final):
+                close(i + 1 - (m["sep_len"] if s == m["box_state"] else 1))
+                coords, label_from = [], None
+            if s in dfa.final:
+                break
+        return out
+
     def batch(self, images: List, texts: List[str], suffixes: Optional[List[str]] = None) -> dict:
         """Several (image, prompt) pairs as one right-padded batch for ``generate`` (the reference handles one pair,
         its ``__call__`` asserts so): each pair goes through ``__call__`` alone -- so every row's ids are exactly its
