@@ -50,7 +50,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const float
                lda >= K && lda % 8 == 0 && ((uintptr_t)A & 15) == 0 && K % 128 == 0 && (K / 128) % ksplit == 0 &&
                (K / 128 / ksplit == 8 || K / 128 / ksplit == 16));
   if (f.amax_out) PG_REQUIRE(fp8 && frag && epi == PG_EPI_BF16_GELU_MUL && M <= 32 && f.amax_ld >= 1 &&
-                             ((K >> 7) + ksplit - 1) / ksplit * 128 <= 4096 && PG_GEMV8_WIDE);
+                             ((K >> 7) + ksplit - 1) / ksplit * 128 <= 4096);
   // (ABI 12: also the bf16 fragment-packed GEMV, which clears the batch-1 decode's fixed-point accumulator with it)
   if (f.amax_zero) PG_REQUIRE((frag || frag13) && f.amax_zero_n >= 0 &&
                               (fp8 ? f.amax_zero_n <= 4096
@@ -92,7 +92,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const float
   // mx_out is written by the wide form only (gemv8x_kernel, NTW 2): launch_gemv8 takes it for GELU_MUL whenever a
   // split's x fits the LDS -- and, with MX rows in, when the split's chunk count is a compile-time 8 or 16
   if (f.mx_out && frag) PG_REQUIRE(fp8 && epi == PG_EPI_BF16_GELU_MUL && M <= 32 && f.pro_mode == 0 && !f.amax_out &&
-                                    ksplit == 1 && (N / 2) % 128 == 0 && PG_GEMV8_WIDE && (K >> 7) * 128 <= 4096 &&
+                                    ksplit == 1 && (N / 2) % 128 == 0 && (K >> 7) * 128 <= 4096 &&
                                     (!f.mx_in || (K >> 7) == 8 || (K >> 7) == 16));
   // (ABI 12) the prefill tile form: e4m3 h [M][ldc bytes] + scales [M][N/64] from the 128 x 128 fp8 tile
   if (f.mx_out && !frag) PG_REQUIRE(fp8 && epi == PG_EPI_BF16_GELU_MUL && M > 32 && f.pro_mode == 0 && !f.mx_in &&

@@ -3,18 +3,24 @@
 // A: activations, bf16 row-major (lda).  W: nn.Linear weight layout [N][K] (ldw),
 // bf16, K zero-padded to a multiple of 64 at pack time.  fp32 accumulation.
 //
-// Two kernels:
-//  * gemm_tile_kernel : 128x128x64 tiles, 4 waves (2x2, 64x64 each), A and W tiles
-//    staged HBM->LDS by global_load_lds (16 B/lane) into a double-buffered,
-//    XOR-swizzled LDS image; mfma_f32_16x16x32_bf16 with the operands swapped
-//    (MFMA-A = W, MFMA-B = A) so each lane ends with 4 consecutive n of one m —
-//    8/16-byte epilogue stores.  Used for prefill (M = tokens).
-//  * gemv_kernel      : M <= 16 (decode).  Weight streaming: each wave reads
+// Kernels:
+//  * gemm_tile_kernel (gemm_tile.hip; prefill, M = tokens): BM x BN x 64 tiles -- 64 x 128, 64 x 64 and 128 x 128
+//    for the general grids, 256 / 288 x 128 for the batch-1 prefill's single row tile -- of 8 waves (4 at 64 x 64,
+//    12 at 288 rows).  A and W k-tiles are staged HBM->LDS by global_load_lds (16 B/lane) into a 2- to 4-stage ring
+//    of XOR-swizzled LDS images behind a counted vmcnt; mfma_f32_16x16x32_bf16 with the operands swapped
+//    (MFMA-A = W, MFMA-B = A) so each lane ends with 4 consecutive n of one m -- 8/16-byte epilogue stores.
+//    fp8 operands (one 16x16x128 MFMA per 128-byte k-row), optionally MX block scales on the A rows.
+//  * gemm256_kernel (gemm_tile.hip; prefill at a few thousand rows): 256 x 256 x 64 tiles, 8 waves, one workgroup
+//    per CU, four half-images per k-tile consumed in four phases with three half-tiles in flight.
+//  * gemm_finalize_kernel (gemm_tile.hip): sums split-K fp32 slabs and applies a bf16 epilogue.
+//  * gemv_kernel and its batch-1 forms (gemm_gemv.hip; M <= 16, decode).  Weight streaming: each wave reads
 //    16 rows of W with 16U-byte contiguous loads per lane straight
 //    into VGPRs (no LDS round trip), the k order inside an MFMA step is permuted
 //    identically for both operands so a lane's bytes are contiguous; 4 waves per
 //    workgroup split K and reduce through LDS; an optional second level of
 //    split-K writes fp32 partial slabs that the next norm kernel reduces.
+//  * gemv8_kernel / gemv8x_kernel (gemm_gemv8.hip; M <= 32, fp8 fragment-packed W): the same streaming with K split
+//    over the waves, or x staged once per workgroup in LDS and N split over the waves.
 //
 // Replaces the nn.Linear call sites of modeling_siglip.py:59-62,177-178,
 // modeling_paligemma.py:57, modeling_gemma.py:205-207,255-259,484.
@@ -27,16 +33,6 @@
 #include <type_traits>
 
 #include "attn_common.h"
-
-#ifndef PG_G256_STAGGER
-#define PG_G256_STAGGER 1       // gemm256: wave groups one barrier apart (MFMA of one || LDS reads of the other); +4-14%
-#endif
-#ifndef PG_G256_F8_BUF
-#define PG_G256_F8_BUF 1        // gemm256 fp8: operand pieces through buffer resources (two lane offsets, no spills)
-#endif
-#ifndef PG_G256_PREFETCH
-#define PG_G256_PREFETCH 1      // gemm256: LDS reads one phase ahead of the MFMAs
-#endif
 
 enum {
   PG_EPI_BF16 = 0,          // C bf16 = acc + bias
@@ -186,11 +182,6 @@ __device__ __forceinline__ f32x4 load4_guard(const float* __restrict__ p, int n0
 #define PG_F13_BLOCK 3328   // ... bytes of one 16-row x 128-k block
 #define PG_W_FRAG12 0x4000  // with PG_W_FRAG13: the pack is the 12-bit form (include/pghip.h), the same launches
 #define PG_F12_BLOCK 3072   // ... bytes of one block of its main array; a wide block's fifth code bits are 256 B more
-
-// fp8 GEMV: the wide form (x once per workgroup in LDS, waves split N), gemm_gemv8.hip; gemm.hip checks against it
-#ifndef PG_GEMV8_WIDE
-#define PG_GEMV8_WIDE 1
-#endif
 
 #define TBN 128   // tile GEMM: output columns per tile
 #define TBK 64    // ... k per stage

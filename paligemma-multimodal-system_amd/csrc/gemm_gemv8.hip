@@ -437,6 +437,7 @@ static void launch_gemv8x_mt(const uint8_t* X, int ldx, const uint8_t* W, int K,
       return;
     }
   }
+  if constexpr (EPI != PG_EPI_F32_ADD)             // (no MX form: pg_dispatch_gemv8)
   if (e.f.mx_in) {                                 // MX rows (launch_gemv8 checked: exact, 8 or 16 chunks)
     if (per_z == 16)
       hipLaunchKernelGGL((gemv8x_kernel<EPI, NTW, MT, DEPTH, 16, false, true>), grid, dim3(256), lds, st, X, ldx, W, K,
@@ -454,16 +455,16 @@ static void launch_gemv8x_mt(const uint8_t* X, int ldx, const uint8_t* W, int K,
     hipLaunchKernelGGL((gemv8x_kernel<EPI, NTW, MT, DEPTH, 0>), grid, dim3(256), lds, st, X, ldx, W, K, e);
 }
 
-#ifndef PG_GEMV8_DEPTH
-#define PG_GEMV8_DEPTH 4
-#endif
+// The K-split form (gemv8_kernel), NT W tiles per workgroup, MT 16-row x tiles; RS: the row split instead of MT 2.
+// Chunks per wave K / 128 / ksplit / 4 a compile-time 2, 4 or 8 when that division is exact, else the runtime loop.
+constexpr int PG_GEMV8_DEPTH = 4;                  // chunks in flight per wave
 template <int EPI, int NT, int MT, bool MX = false, bool RS = false>
 static void launch_gemv8_mt(const uint8_t* X, int ldx, const uint8_t* W, int K, int ksplit, const EpiArgs& e,
                             hipStream_t st) {
   const dim3 grid(((e.N >> 4) + NT - 1) / NT, ksplit, RS ? (e.M + 15) / 16 : 1);
   const int nch = K >> 7;
   const int cpw = (nch % ksplit == 0 && (nch / ksplit) % 4 == 0) ? nch / ksplit / 4 : 0;
-  constexpr int D = PG_GEMV8_DEPTH;                // chunks in flight per wave
+  constexpr int D = PG_GEMV8_DEPTH;
   switch (cpw) {
     case 2: hipLaunchKernelGGL((gemv8_kernel<EPI, NT, MT, 2, 2, MX, RS>), grid, dim3(256), 0, st, X, ldx, W, K, e); break;
     case 4: hipLaunchKernelGGL((gemv8_kernel<EPI, NT, MT, D, 4, MX, RS>), grid, dim3(256), 0, st, X, ldx, W, K, e); break;
@@ -472,78 +473,74 @@ static void launch_gemv8_mt(const uint8_t* X, int ldx, const uint8_t* W, int K, 
   }
 }
 
-#ifndef PG_GEMV8_ROWSPLIT
-#define PG_GEMV8_ROWSPLIT 1
-#endif
+// ... its rows: q|k|v and the fp32 slabs at 17..32 rows with a grid short of two workgroups per CU split the rows over
+// blockIdx.z (the row split doubles the grid); else one x tile at M <= 16, two above.  MX rows in: the MX kernels
+// (F32_ADD has none: pg_dispatch_gemv8).
 template <int EPI, int NT>
 static void launch_gemv8_nt(const uint8_t* X, int ldx, const uint8_t* W, int K, int ksplit, const EpiArgs& e,
                             hipStream_t st) {
+  constexpr bool MXE = EPI != PG_EPI_F32_ADD;
+  const bool mx = MXE && e.f.mx_in != nullptr;
   if constexpr (EPI == PG_EPI_QKV_ROPE || EPI == PG_EPI_F32) {
-    // (a grid short of two workgroups per CU: the row split doubles it)
-    if (PG_GEMV8_ROWSPLIT && e.M > 16 && ((e.N >> 4) + NT - 1) / NT * ksplit < 512) {
-      if (e.f.mx_in) launch_gemv8_mt<EPI, NT, 1, true, true>(X, ldx, W, K, ksplit, e, st);
+    if (e.M > 16 && ((e.N >> 4) + NT - 1) / NT * ksplit < 512) {
+      if (mx) launch_gemv8_mt<EPI, NT, 1, true, true>(X, ldx, W, K, ksplit, e, st);
       else launch_gemv8_mt<EPI, NT, 1, false, true>(X, ldx, W, K, ksplit, e, st);
       return;
     }
   }
-  if (e.f.mx_in) {
-    if (e.M <= 16) launch_gemv8_mt<EPI, NT, 1, true>(X, ldx, W, K, ksplit, e, st);
-    else launch_gemv8_mt<EPI, NT, 2, true>(X, ldx, W, K, ksplit, e, st);
-    return;
+  if (e.M <= 16) {
+    if (mx) launch_gemv8_mt<EPI, NT, 1, MXE>(X, ldx, W, K, ksplit, e, st);
+    else launch_gemv8_mt<EPI, NT, 1>(X, ldx, W, K, ksplit, e, st);
+  } else {
+    if (mx) launch_gemv8_mt<EPI, NT, 2, MXE>(X, ldx, W, K, ksplit, e, st);
+    else launch_gemv8_mt<EPI, NT, 2>(X, ldx, W, K, ksplit, e, st);
   }
-  if (e.M <= 16)
-    launch_gemv8_mt<EPI, NT, 1>(X, ldx, W, K, ksplit, e, st);
-  else
-    launch_gemv8_mt<EPI, NT, 2>(X, ldx, W, K, ksplit, e, st);
 }
 
-#ifndef PG_GEMV8_NT_MAX
-#define PG_GEMV8_NT_MAX 4
-#endif
-// NT W tiles per workgroup: every lane loads the x rows of its chunks once per workgroup, as many bytes per 16-row W
-// tile as the tile itself at 32 rows, so wide tiles amortise x -- the most tiles per workgroup that still leave
-// >= 256 workgroups (gelu*up: whole gate/up pairs); MT = 16-row x tiles
+// ... the wide form's x tiles: one at M <= 16, two above
+template <int EPI, int NTW>
+static void launch_gemv8x(const uint8_t* X, int ldx, const uint8_t* W, int K, int ksplit, const EpiArgs& e,
+                          hipStream_t st) {
+  if (e.M <= 16) launch_gemv8x_mt<EPI, NTW, 1>(X, ldx, W, K, ksplit, e, st);
+  else launch_gemv8x_mt<EPI, NTW, 2>(X, ldx, W, K, ksplit, e, st);
+}
+
+// The form of one fp8 GEMV (tests/test_gemm_exact_gpu.py gemv8_form restates it).  tiles = N / 16, per_z = chunks
+// (128 k) of a split.
 template <int EPI>
 static void launch_gemv8(const uint8_t* X, int ldx, const uint8_t* W, int K, int ksplit, const EpiArgs& e,
                          hipStream_t st) {
+  constexpr bool PAIRS = EPI == PG_EPI_BF16_GELU_MUL;    // whole gate/up pairs: never one tile per wave / workgroup
   const int tiles = e.N >> 4;
-  // the wide form (x once per workgroup in LDS, waves split N) when its grid still has >= 256 workgroups and a
-  // split's x rows fit the LDS; the K-split form otherwise (q|k|v: 160 tiles; o_proj)
   const int per_z = ((K >> 7) + ksplit - 1) / ksplit;
+  const int wgs2 = (tiles + 7) / 8 * ksplit, wgs1 = (tiles + 3) / 4 * ksplit;   // wide grids at 2 / 1 tiles per wave
+  // 1. bf16 x quantised while staged (pro_mode 5): the wide form only (host checked the chunk count)
   if constexpr (EPI == PG_EPI_F32) {
-    if (e.f.pro_mode == 5) {                       // bf16 x: the wide form only (host checked the chunk count)
-      const int wgs2 = (tiles + 7) / 8 * ksplit;
-      if (e.M <= 16) {
-        if (wgs2 >= 256) launch_gemv8x_mt<EPI, 2, 1>(X, ldx, W, K, ksplit, e, st);
-        else launch_gemv8x_mt<EPI, 1, 1>(X, ldx, W, K, ksplit, e, st);
-      } else {
-        if (wgs2 >= 256) launch_gemv8x_mt<EPI, 2, 2>(X, ldx, W, K, ksplit, e, st);
-        else launch_gemv8x_mt<EPI, 1, 2>(X, ldx, W, K, ksplit, e, st);
-      }
+    if (e.f.pro_mode == 5) {
+      if (wgs2 >= 256) launch_gemv8x<EPI, 2>(X, ldx, W, K, ksplit, e, st);
+      else launch_gemv8x<EPI, 1>(X, ldx, W, K, ksplit, e, st);
       return;
     }
   }
-  // (MX rows take the wide form only when its chunk count is a compile-time 8 or 16)
+  // 2. the wide form (x once per workgroup in LDS, waves split N) when a split's x rows fit the LDS -- MX rows: only
+  //    at a compile-time 8 or 16 chunks -- and its grid still has >= 256 workgroups, at two tiles per wave or at one
+  //    (not q|k|v: 160 tiles)
   const bool mx_ok = !e.f.mx_in || ((K >> 7) % ksplit == 0 && (per_z == 8 || per_z == 16));
   if constexpr (EPI != PG_EPI_QKV_ROPE) {
-    if (PG_GEMV8_WIDE && per_z * 128 <= 4096 && mx_ok) {
-      const int wgs2 = (tiles + 7) / 8 * ksplit, wgs1 = (tiles + 3) / 4 * ksplit;
-      if (e.M <= 16) {
-        if (wgs2 >= 256 || EPI == PG_EPI_BF16_GELU_MUL) { launch_gemv8x_mt<EPI, 2, 1>(X, ldx, W, K, ksplit, e, st); return; }
-        if constexpr (EPI != PG_EPI_BF16_GELU_MUL)
-          if (wgs1 >= 256) { launch_gemv8x_mt<EPI, 1, 1>(X, ldx, W, K, ksplit, e, st); return; }
-      } else {
-        if (wgs2 >= 256 || EPI == PG_EPI_BF16_GELU_MUL) { launch_gemv8x_mt<EPI, 2, 2>(X, ldx, W, K, ksplit, e, st); return; }
-        if constexpr (EPI != PG_EPI_BF16_GELU_MUL)
-          if (wgs1 >= 256) { launch_gemv8x_mt<EPI, 1, 2>(X, ldx, W, K, ksplit, e, st); return; }
-      }
+    if (per_z * 128 <= 4096 && mx_ok) {
+      if (wgs2 >= 256 || PAIRS) return launch_gemv8x<EPI, 2>(X, ldx, W, K, ksplit, e, st);
+      if constexpr (!PAIRS)
+        if (wgs1 >= 256) return launch_gemv8x<EPI, 1>(X, ldx, W, K, ksplit, e, st);
     }
   }
-  if (PG_GEMV8_NT_MAX >= 4 && tiles % 4 == 0 && (tiles / 4) * ksplit >= 256)
+  // 3. the K-split form, NT W tiles per workgroup: every lane loads the x rows of its chunks once per workgroup, as many
+  //    bytes per 16-row W tile as the tile itself at 32 rows, so wide tiles amortise x -- the most tiles per workgroup
+  //    (4, 2, 1) that still leave >= 256 workgroups
+  if (tiles % 4 == 0 && (tiles / 4) * ksplit >= 256)
     launch_gemv8_nt<EPI, 4>(X, ldx, W, K, ksplit, e, st);
-  else if (EPI == PG_EPI_BF16_GELU_MUL || (PG_GEMV8_NT_MAX >= 2 && tiles % 2 == 0 && (tiles / 2) * ksplit >= 256))
+  else if (PAIRS || (tiles % 2 == 0 && (tiles / 2) * ksplit >= 256))
     launch_gemv8_nt<EPI, 2>(X, ldx, W, K, ksplit, e, st);
-  else if constexpr (EPI != PG_EPI_BF16_GELU_MUL)
+  else if constexpr (!PAIRS)
     launch_gemv8_nt<EPI, 1>(X, ldx, W, K, ksplit, e, st);
 }
 
@@ -554,7 +551,11 @@ int pg_dispatch_gemv8(int epi, const uint8_t* X, int ldx, const uint8_t* W, int 
     case PG_EPI_BF16_GELU_MUL: launch_gemv8<PG_EPI_BF16_GELU_MUL>(X, ldx, W, K, ksplit, e, st); return 0;
     case PG_EPI_F32: launch_gemv8<PG_EPI_F32>(X, ldx, W, K, ksplit, e, st); return 0;
     case PG_EPI_QKV_ROPE: launch_gemv8<PG_EPI_QKV_ROPE>(X, ldx, W, K, ksplit, e, st); return 0;
-    case PG_EPI_F32_ADD: launch_gemv8<PG_EPI_F32_ADD>(X, ldx, W, K, ksplit, e, st); return 0;
+    case PG_EPI_F32_ADD:
+      // (no MX-row instances: gemm_impl refuses mx_in with F32_ADD -- its `f.mx_in && frag` check)
+      if (e.f.mx_in) return (int)hipErrorInvalidValue;
+      launch_gemv8<PG_EPI_F32_ADD>(X, ldx, W, K, ksplit, e, st);
+      return 0;
     default: return (int)hipErrorInvalidValue;
   }
 }

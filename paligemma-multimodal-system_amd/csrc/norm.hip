@@ -10,9 +10,6 @@
 #include "common.h"
 
 #define NORM_MAXV 4   // float4 per thread -> H <= 4096
-#ifndef PG_NORM_W_EARLY
-#define PG_NORM_W_EARLY 1   // norm weights / bias loaded with the residual (not after the reductions)
-#endif
 // Split-K slabs loaded per round (SG) and float4 slots per thread (MAXV) are template parameters: 8 slabs per round
 // pays where few rows carry many slabs (batch-1 prefill: 16-slab down projection), but its 214 registers (two
 // waves per SIMD) tripled the 16 k-row norms of pt-448 x16 (55 -> 151 us each, 85 -> 93 ms per prefill): large
@@ -39,7 +36,7 @@ __global__ __launch_bounds__(256) void norm_residual_kernel(float* __restrict__ 
   f32x4 wv[MAXV], bv[MAXV];
 #pragma unroll
   for (int i = 0; i < MAXV; ++i)
-    if (PG_NORM_W_EARLY && i < nv) {
+    if (i < nv) {
       const int c = min((int)threadIdx.x + i * 256, H4 - 1);
       wv[i] = ((const f32x4*)w)[c];
       bv[i] = mode == 0 ? ((const f32x4*)b)[c] : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -108,10 +105,6 @@ __global__ __launch_bounds__(256) void norm_residual_kernel(float* __restrict__ 
     const int c = threadIdx.x + i * 256;
     if (c < H4) {
       f32x4 y;
-      if (!PG_NORM_W_EARLY) {
-        wv[i] = ((const f32x4*)w)[c];
-        bv[i] = mode == 0 ? ((const f32x4*)b)[c] : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
       if (mode == 0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) y[j] = (v[i][j] - mean) * rstd * wv[i][j] + bv[i][j];

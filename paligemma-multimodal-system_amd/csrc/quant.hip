@@ -127,9 +127,7 @@ __global__ __launch_bounds__(256) void quant_fp8_wave_kernel(const bf16_t* __res
   }
 }
 
-#ifndef PG_QUANT_WAVE_MIN_M
-#define PG_QUANT_WAVE_MIN_M 1024   // rows from which the wave-per-row form is used
-#endif
+constexpr int PG_QUANT_WAVE_MIN_M = 1024;   // rows from which the wave-per-row form is used
 
 // x bf16 [M][K] (row stride ldx) -> q fp8 e4m3 [M][K] (row stride ldq bytes), scale f32 [M].
 // K % 8 == 0, ldx % 8 == 0, ldq % 8 == 0, 16-byte aligned x.

@@ -148,7 +148,7 @@ def gemm8(A8: torch.Tensor, a_scale: Optional[torch.Tensor], W8: torch.Tensor, w
         if mx_in is None or ss_in.stride(-1) != 1 or K % 1024 or not 0 < K // 1024 <= 4 or ss_in.shape[-1] < K // 1024:
             raise ValueError("pghip.gemm8: ss_in needs mx_in and fp32 [M][K/1024] sums of squares (K <= 4096)")
         fa.ss_in, fa.ss_ld, fa.ss_n, fa.eps = ss_in.data_ptr(), ss_in.stride(-2), K // 1024, float(eps)
-    e = epi & (0xFF | SLOT_ROWS)
+    e = epi & (0xFF | SLOT_ROWS | TILE_N64)
     ldc = out.stride(-2) if out.dim() >= 2 else out.shape[-1]
     if frag:
         if M > 32:
@@ -160,8 +160,9 @@ def gemm8(A8: torch.Tensor, a_scale: Optional[torch.Tensor], W8: torch.Tensor, w
     if s > 1:   # small M: fp32 slabs, then the epilogue (scales already applied inside the slabs)
         part = torch.empty(s, M, N, dtype=torch.float32, device=out.device)
         _lib.call("pg_gemm_fused", _p(A8), A8.stride(0), _p(W8), W8.stride(0), _p(bias), _p(part), N, M, N, K,
-                  EPI_F32 | EPI_FP8, s, _lib.C.byref(fa), _s())
-        _lib.call("pg_gemm_finalize", _p(part), s, _p(out), ldc, M, N, e, None, 0, 0, _lib.C.byref(fa), _s())
+                  EPI_F32 | EPI_FP8 | (e & TILE_N64), s, _lib.C.byref(fa), _s())
+        _lib.call("pg_gemm_finalize", _p(part), s, _p(out), ldc, M, N, e & ~TILE_N64, None, 0, 0, _lib.C.byref(fa),
+                  _s())
         return out
     _lib.call("pg_gemm_fused", _p(A8), A8.stride(0), _p(W8), W8.stride(0), _p(bias), _p(out), ldc, M, N, K,
               e | EPI_FP8, ksplit, _lib.C.byref(fa), _s())

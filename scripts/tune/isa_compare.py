@@ -1,7 +1,9 @@
-"""Per-kernel comparison of two hipcc gfx950 assembly files of one source (profiles/attn_refactor_isa.txt).
+"""Per-kernel comparison of two hipcc gfx950 assembly files of one source (profiles/attn_refactor_isa.txt,
+profiles/gemm_refactor_isa.txt).
 
-    hipcc -O3 --offload-arch=gfx950 <the build's flags> --cuda-device-only -S csrc/attn.hip -o attn.s   (both trees)
-    python scripts/tune/isa_compare.py parent/attn.s new/attn.s [--allow REGEX]
+    hipcc -O3 --offload-arch=gfx950 <the build's flags of pghip/build.py, with its preload flags for the sources that
+          take them> --cuda-device-only -S csrc/SOURCE.hip -o SOURCE.s                                (both trees)
+    python scripts/tune/isa_compare.py parent/SOURCE.s new/SOURCE.s [--allow REGEX] [--rename REGEX REPL]
 
 For a refactor that removes kernel instances, whole-text comparison fails on the renumbered function-indexed local
 labels alone.  This compares, per kernel symbol: the symbol sets, each body (label line to the end of the function's
@@ -9,6 +11,10 @@ text, the function index in local labels dropped) and each .amdhsa_kernel descri
 differences only and looks at no instruction.  For a kernel that differs it prints the body line counts and the
 descriptor lines that differ (the register counts are there).  Exit status 1 if a kernel outside --allow (a regex on
 the demangled-ish short name) differs or a symbol was added.
+
+--rename REGEX REPL: a refactor that drops a template parameter renames every instance of that kernel.  The parent's
+mangled symbols are rewritten with re.sub(REGEX, REPL) before the sets are compared, so such an instance is compared
+with its successor instead of being counted once as removed and once as added; the renamed count is printed.
 """
 import hashlib
 import re
@@ -79,7 +85,18 @@ def main():
         i = args.index("--allow")
         allow = re.compile(args[i + 1])
         del args[i:i + 2]
+    rename = None
+    if "--rename" in args:
+        i = args.index("--rename")
+        rename = (re.compile(args[i + 1]), args[i + 2])
+        del args[i:i + 3]
     old, new = kernels(args[0]), kernels(args[1])
+    if rename:
+        n = len(old)
+        renamed = {rename[0].sub(rename[1], k): v for k, v in old.items()}
+        assert len(renamed) == n, "--rename maps two parent symbols onto one"
+        print(f"renamed {sum(k not in old for k in renamed)} parent symbols: s/{rename[0].pattern}/{rename[1]}/")
+        old = renamed
     gone, added = sorted(set(old) - set(new)), sorted(set(new) - set(old))
     both = sorted(set(old) & set(new))
     print(f"kernels: {len(old)} -> {len(new)}; removed {len(gone)}, added {len(added)}, in both {len(both)}")

@@ -661,11 +661,12 @@ def _fp8_operands(p, frag=False):
 
 
 # fp8 launch_tile (no auto 64 x 64): 100 x 300 and 300 x 704 -> 64 x 128 (2 * 3 and 5 * 6 workgroups); 1100 x 3712 ->
-# 128 x 128; 4113 x 3856 -> 256 x 256 for F32 / F32_RES only (PG_F8_G256 == 1), the 128 x 128 tile for BF16.
-# (ops.gemm8 does not pass PG_TILE_N64 on, so the fp8 64 x 64 tile is out of these tests' reach.)
+# 128 x 128; 4113 x 3856 -> 256 x 256 for F32 / F32_RES only, the 128 x 128 tile for BF16; 300 x 704 with PG_TILE_N64
+# -> 64 x 64.
 @pytest.mark.parametrize("K", [128, 384])
 @pytest.mark.parametrize("M,N,flags,route", [(100, 300, 0, "t64x128"), (300, 704, 0, "t64x128"),
-                                             (1100, 3712, 0, "t128x128"), (4113, 3856, 0, "g256")])
+                                             (1100, 3712, 0, "t128x128"), (4113, 3856, 0, "g256"),
+                                             (300, 704, 0x800, "t64x64-flag")])
 def test_fp8_tile_routes_exact(M, N, flags, route, K):
     """ops.gemm8 on the tile routes at one and three 128-k tiles: F32 at ks 1 and a ragged ks 2, F32_RES and BF16, exact
     with power-of-two row scales."""
