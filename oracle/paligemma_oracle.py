@@ -55,11 +55,12 @@ class bf16_operands:
 # for 17..32-row batches (engine._lm_gemm, the fp8 GEMV) and in bf16 otherwise; lm_head=True emulates the e4m3 form
 # (tests/golden/make_emu.py sets it for the batch-32 fixtures).
 # mx_h=True: a down_proj call of at most 32 rows (batched decode) takes MX rows instead -- h rounded to bf16, then
-# e4m3 with one power-of-two scale per 32 contiguous columns (engine.MX_H: the gate/up epilogue's mx_out rule,
-# csrc/common.h mx_exp), the weights per-channel as before.  mx_norm=True: the RMSNorm-fed linears of at most 32
-# rows (q|k|v, gate/up, the lm_head) take MX rows of the normalised input too (engine.MX_NORM: pg_norm_residual_mx
-# quantises x*(1+w) per 32-column block and the GEMV applies rstd to its outputs -- the same block-relative e4m3
-# rounding; emulated on the normalised row, so per-element bits differ where rstd is not a power of two).
+# e4m3 with one power-of-two scale per 32 contiguous columns (the engine's 17..32-row fp8 decode MLP: the gate/up
+# epilogue's mx_out rule, csrc/common.h mx_exp), the weights per-channel as before.  mx_norm=True: the RMSNorm-fed
+# linears of at most 32 rows (q|k|v, gate/up, the lm_head) take MX rows of the normalised input too (the norms of that
+# decode route: pg_norm_residual_mx quantises x*(1+w) per 32-column block and the GEMV applies rstd to its outputs --
+# the same block-relative e4m3 rounding; emulated on the normalised row, so per-element bits differ where rstd is not
+# a power of two).
 # tp=W (> 1): the tensor-parallel form of the HIP path (engine.tp): the row-parallel o_proj and
 # down_proj run on W equal K slices -- each rank quantises its slice of the activation row and its slice of every
 # weight row with their own max/448 scales (weights.PackedWeights(tp_world=W) / pg_quant_fp8 on the local slice; MX
@@ -71,8 +72,8 @@ _FP8_LM_HEAD = False
 _FP8_MX_H = False
 _FP8_MX_NORM = False
 _FP8_TP = 1
-# mx_h_prefill=True (round 6, engine.MX_PREFILL): a down_proj call of MORE than 32 rows (the prefill) takes MX rows of
-# h as well -- the fp8 gate/up tile's epilogue writes e4m3 h with one E8M0 scale per 32 columns
+# mx_h_prefill=True (round 6, the engine's fp8 prefill MLP): a down_proj call of MORE than 32 rows (the prefill) takes
+# MX rows of h as well -- the fp8 gate/up tile's epilogue writes e4m3 h with one E8M0 scale per 32 columns
 _FP8_MX_HP = False
 
 

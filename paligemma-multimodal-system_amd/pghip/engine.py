@@ -13,9 +13,11 @@ HIP kernels:
   decode step                the same per token with the GEMV kernels, split-KV attention, argmax / top-p;
                              every per-step scalar (kv length, positions, step) lives in device memory,
                              so one step is captured once as a hipGraph and replayed.  The layers run in one
-                             of three forms (_decode_route):
-                               fin      one rank, bf16 rows, B <= FUSE_MAX_B or FIN_MIN_B <= B <= 16: o_proj and
-                                        down_proj finalise their split-K partials in-kernel (_decode_layers_fin);
+                             of three routes (_decode_route), the first in two forms:
+                               fin      one rank, bf16 rows.  B <= FUSE_MAX_B: o_proj and down_proj add into a
+                                        fixed-point residual, norm and merge as GEMV prologues (_decode_layers_fx);
+                                        FIN_MIN_B <= B <= 16: o_proj and down_proj finalise their split-K partials
+                                        in-kernel, the merge is its own kernel (_decode_layers_fin);
                                fused    B <= FUSE_MAX_B otherwise (tensor parallel, USE_FIN off): RMSNorm and
                                         attention merge as GEMV prologues, fp32 slabs (_decode_layers_fused);
                                unfused  every other batch (3..4 and > 16 rows, fp8 rows, TP above FUSE_MAX_B): norm
@@ -136,70 +138,29 @@ class PaliGemmaEngine:
     DECODE_SPLIT_KEYS = 32  # keys per wave in split-KV decode attention (one MFMA block)
     # keys per split at B <= FUSE_MAX_B: every o_proj workgroup merges all active splits in its prologue, so
     # fewer, longer splits (one wave per 32 keys, merged in LDS by attn_decode_wg_kernel) cut that re-read
-    DECODE_SPLIT_KEYS_SMALL = int(os.environ.get("PG_SK_SMALL", "32"))
+    DECODE_SPLIT_KEYS_SMALL = 32
     # prefill GEMMs of at least this many rows read the row-major weight copies (weights.prefill_rowmajor)
-    PREFILL_ROWMAJOR_MIN_M = int(os.environ.get("PG_ROWMAJOR_MIN_M", "256"))
-    ROW_BLOCKS = os.environ.get("PG_ROW_BLOCKS", "1") != "0"   # ragged fp32-slab GEMMs as head + tail launches
-    TAIL_SPLIT = os.environ.get("PG_TAIL_SPLIT", "1") != "0"   # ... the tail with its own deeper split-K
-    HEAD_KSPLIT = os.environ.get("PG_HEAD_KSPLIT", "1") != "0"  # ... and the split-K chosen for the head
-    ROW_BLOCKS_GU = os.environ.get("PG_ROW_BLOCKS_GU", "1") != "0"  # gate/up (bf16 gelu*up) as row blocks too
-    # batch-1 prefill (256 <= rows <= 288): these Gemma linears run as ONE row tile per 128 columns (PG_TILE_M1),
-    # with this split-K -- each weight tile streams once instead of once per 256-row tile.  Per call at 264 rows
-    # (scripts/tune/skinny_bench.py, profiles/r02_skinny_gemm_*.txt): gate/up 60.8 -> 52.8 us, down 38.9 -> 33.5,
-    # o 15.2 -> 14.1.  The q|k|v / SigLIP epilogues cannot split K, so their one-tile grids would idle most CUs.
-    TILE_M1 = os.environ.get("PG_TILE_M1", "1") != "0"
-    # (o left the table: 64-row tiles at split 3 take 10.3 us against 12.7-13.5 for one row tile at split 8-12,
-    # and leave 3 slabs instead of 8 for the RMSNorm; profiles/r03_tile_sweep.txt)
-    TILE_M1_SPLIT = {"gu": 1, "down": int(os.environ.get("PG_M1_DOWN", "16"))}
+    PREFILL_ROWMAJOR_MIN_M = 256
+    # batch-1 prefill (256 <= rows <= 288, one rank, bf16): gate/up and down run as ONE row tile per 128 columns
+    # (ops.TILE_M1) with this split-K -- each weight tile streams once instead of once per 256-row tile.  The q|k|v /
+    # SigLIP epilogues cannot split K, so their one-tile grids would idle most CUs; o_proj runs faster on 64-row tiles
+    TILE_M1_SPLIT = {"gu": 1, "down": 16}
     FUSE_MAX_B = 2          # decode batches up to this size fuse RMSNorm / attention merge into the GEMVs
     DECODE_SPLIT_TARGET = 1024  # B > FUSE_MAX_B: aim for about this many decode-attention splits (waves)
     FIN_MIN_B = 5           # FIN_MIN_B <= B <= 16: in-kernel finalisation with the merge as its own kernel
-    USE_FIN = True          # single rank: split-K slabs finalised in-kernel (see _decode_layers_fin)
-    # tensor parallel: SigLIP data-parallel over the images when every rank gets at least one (else replicated)
-    VISION_DP = os.environ.get("PG_VISION_DP", "1") != "0"
+    USE_FIN = True          # single rank: the fx / fin decode layers (off: the fused form, as under tensor parallelism)
     # tensor-parallel prefill: rows per all-reduce chunk (each chunk's all-reduce overlaps the next chunk's GEMM)
-    AR_CHUNK_ROWS = int(os.environ.get("PG_AR_CHUNK_ROWS", "4096"))
+    AR_CHUNK_ROWS = 4096
     # chained greedy decode (single rank): the argmax's final launch also writes the next step's input rows
     # (pg_argmax_embed), so a decode step starts at layer 0 with no embed launch (decode_state(sampler=...))
-    CHAIN_EMBED = os.environ.get("PG_CHAIN_EMBED", "1") != "0"
-    # 17..32-row fp8 decode MLP on MX rows: the gate/up epilogue writes h as e4m3 with one E8M0 scale per 32
-    # columns (PgFusedArgs.mx_out) and the down GEMV reads those block scales into its MFMAs (mx_in) -- no
-    # quantiser launch and no cross-workgroup row maximum (the block max stays inside one workgroup)
-    MX_H = os.environ.get("PG_MX_H", "1") != "0"
-    # ... and the RMSNorms in front of the q|k|v, gate/up and lm_head GEMVs write MX rows of x*(1+w) with per-1024-column
-    # sums of squares (pg_norm_residual_mx: one workgroup per 1024 columns and row, no row-wide reduction); the GEMV applies
-    # rstd to its outputs.  Replaces the norm + per-row quantiser pair
-    MX_NORM = os.environ.get("PG_MX_NORM", "1") != "0"
-    # fp8 prefill MLP on MX h too (ABI 12): the 128 x 128 fp8 gate/up tile writes h as e4m3 + one E8M0 scale per 32
-    # columns (each wave owns one block per row) and the 128 x 128 fp8 down GEMM (every MX launch runs on that tile)
-    # stages the block scales beside h --
-    # the row quantiser launch between them (and half of h's bytes) is gone
-    MX_PREFILL = os.environ.get("PG_MX_PREFILL", "1") != "0"
+    CHAIN_EMBED = True
     # prefill linears that end a residual branch (SigLIP o / fc2, Gemma o / down) with ONE split on one rank add into
-    # the residual in their epilogue (PG_EPI_F32_RES, ABI 13): the next norm reads the residual alone, 4 B per element
-    # less than a slab write + slab read + residual rewrite; bit-identical (the same one fp32 add)
-    PREFILL_RES = os.environ.get("PG_PREFILL_RES", "1") != "0"
-    # ... from this many rows on: pt-896 x32 prefill 672-675 -> 665-667 ms; at pt-448 x16 (16 k rows) level to 0.5%
-    # slower (85.4-85.6 vs 84.9-85.1 ms; profiles/r06_prefill_res_ab.jsonl), so off there
-    PREFILL_RES_MIN_M = int(os.environ.get("PG_PREFILL_RES_MIN_M", "65536"))
-
-    # B > FUSE_MAX_B: split-KV attention and its merge in one launch (pg_attn_decode; 0 = split kernel + combine)
-    DECODE_FUSED_ATTN = os.environ.get("PG_DECODE_FUSED", "1") != "0"
-    FUSED_MIN_ROUNDS = int(os.environ.get("PG_FUSED_MIN_ROUNDS", "2"))   # ... used from this many rounds per split on
-    # fp8 decode (> 16 rows): the one-launch attention also writes its rows as e4m3 for the fp8 o_proj (no
-    # pg_quant_fp8 launch; same bytes)
-    ATTN_FP8_OUT = os.environ.get("PG_ATTN_FP8_OUT", "1") != "0"
-    # B <= FUSE_MAX_B single rank: row-parallel decode linears that add their split-K partials straight into the
-    # residual instead of finalising slabs in-kernel (F32_FIN's slab store -> ticket -> slab load tail); the next GEMV
-    # then normalises the residual itself (PRO_RMSNORM).  "fx" (default): o_proj and down_proj add into a fixed-point
-    # int64 accumulator with integer atomics (PG_EPI_FX_ADD) -- the sum is exact, so decode is bit-reproducible run to
-    # run; "both": the same with float atomics into the fp32 residual (unordered: ~1 ulp run-to-run drift); "down":
-    # down_proj only, float atomics; "0": off (F32_FIN, deterministic).  The last layer's down_proj always finalises
-    # (F32_FIN), its x' and sums of squares feeding the lm_head
-    DECODE_ADD = os.environ.get("PG_DECODE_ADD", "fx")
-    # fp8 linears of 17..32 rows (batched decode, the lm_head of a 17..32-row batch) on the weight-streaming fp8 GEMV
-    # (fragment-packed e4m3 weights, csrc/gemm.hip gemv8_kernel) instead of the LDS-staged fp8 tile GEMM
-    FP8_GEMV = os.environ.get("PG_FP8_GEMV", "1") != "0"
+    # the residual in their epilogue (EPI_F32_RES) from this many rows on: the next norm reads the residual alone, 4 B
+    # per element less than a slab write + slab read + residual rewrite; bit-identical (the same one fp32 add)
+    PREFILL_RES_MIN_M = 65536
+    # B > FUSE_MAX_B: split-KV attention and its merge in one launch (pg_attn_decode) from this many rounds per split
+    # on; below, the split kernel + pg_attn_combine
+    FUSED_MIN_ROUNDS = 2
     # B <= FUSE_MAX_B single rank, bf16: the decode GEMVs stream the lossless 13-bit weight pack (weights.frag13_pack,
     # PG_W_FRAG13) where a matrix has one -- same bits out, 18.75 % fewer weight bytes in.  W13_FORMS: the
     # launches that take it (a form that does not beat its PG_W_FRAG twin in the kernel profile leaves this list)
@@ -247,14 +208,12 @@ class PaliGemmaEngine:
         w = self.w
         if not hasattr(w, "heads"):                     # vision-only pack (modeling_siglip.SiglipVisionModel)
             return
-        checks = [("o_proj (PG_SPLIT_O)", self.split_o, w.heads * w.head_dim, 8),
-                  ("o_proj at batch <= 2", self.DECODE_SPLIT_O_SMALL, w.heads * w.head_dim, 8),
-                  ("down_proj (PG_SPLIT_DOWN)", self.split_down, w.inter, 8)]
-        if self.TILE_M1:    # (a model too narrow for this split just skips the row-tile path, _tile_m1)
-            checks.append(("batch-1 prefill down_proj (PG_M1_DOWN)", self.TILE_M1_SPLIT["down"], 64 * 64, 64))
-        for what, ks, K, hi in checks:          # (a split past K's 64-wide chunks just computes a zero slab)
-            if not 1 <= ks <= hi:
-                raise ValueError(f"split-K {ks} for {what}: needs 1 <= split <= {hi} (K = {K})")
+        checks = [("o_proj (PG_SPLIT_O)", self.split_o, w.heads * w.head_dim),
+                  ("o_proj at batch <= 2", self.DECODE_SPLIT_O_SMALL, w.heads * w.head_dim),
+                  ("down_proj (PG_SPLIT_DOWN)", self.split_down, w.inter)]
+        for what, ks, K in checks:              # (a split past K's 64-wide chunks just computes a zero slab)
+            if not 1 <= ks <= 8:
+                raise ValueError(f"split-K {ks} for {what}: needs 1 <= split <= 8 (K = {K})")
 
     def _buf(self, name, shape, dtype):
         t = self._ws.get(name)
@@ -286,7 +245,7 @@ class PaliGemmaEngine:
         w = self.w
         px = pixel_values.to(device=self.device, dtype=torch.float32).contiguous()
         B = px.shape[0]
-        if (_split_batch is None and self.tp > 1 and self.VISION_DP and B >= self.tp and B % self.tp == 0
+        if (_split_batch is None and self.tp > 1 and B >= self.tp and B % self.tp == 0
                 and not want_hidden and taps is None and w.proj_w is not None):
             # data-parallel over the images (output-invariant): this rank encodes its B/W images,
             # then the projected features [B*N][P] are all-gathered in rank order = image order.  The rank-local
@@ -314,7 +273,7 @@ class PaliGemmaEngine:
         s_2 = ops.gemm_ksplit(Bs * N, hv, w.v_inter)
         ks_v = self._key_split_args("v", Bs, N, N, nh, nh, hd)
         part = self._buf("v_part", (max(s_o, s_2), M, hv), torch.float32)
-        res = self.PREFILL_RES and M >= max(17, self.PREFILL_RES_MIN_M)
+        res = M >= max(17, self.PREFILL_RES_MIN_M)       # one-split o / fc2 add into the residual (EPI_F32_RES)
         res_o, res_2 = res and s_o == 1, res and s_2 == 1
         ns = 0
         for L in w.vl:
@@ -454,26 +413,31 @@ class PaliGemmaEngine:
         return self.fp8 and M > 16
 
     def _mx_prefill(self, M: int) -> bool:
-        """The fp8 prefill MLP on MX h (MX_PREFILL): the tile GEMMs (more than 32 rows) with row-major fp8 weights."""
+        """The fp8 prefill MLP on MX h: the tile GEMMs (more than 32 rows) with row-major fp8 weights.  The 128 x 128
+        fp8 gate/up tile writes h as e4m3 with one E8M0 scale per 32 columns (PgFusedArgs.mx_out) and the fp8 down GEMM
+        stages those block scales beside h (mx_in) -- no row quantiser launch between them."""
         L0 = self.w.tl[0]
         # (under TP the down projection may run as row chunks (_row_parallel): each must keep > 32 rows)
         chunks_ok = self.tp == 1 or M < 2 * self.AR_CHUNK_ROWS or self.AR_CHUNK_ROWS >= 64
-        return (self.MX_PREFILL and self._fp8_rows(M) and M > 32 and "gu_w8" in L0 and "down_w8" in L0
-                and self.w.inter % 128 == 0 and chunks_ok)
+        return (self._fp8_rows(M) and M > 32 and "gu_w8" in L0 and "down_w8" in L0 and self.w.inter % 128 == 0
+                and chunks_ok)
 
     def _mx_decode(self, B: int) -> tuple:
-        """(MX h, MX norms) for a B-row decode step: the 17..32-row fp8 GEMV path with the packed fp8 weights"""
+        """(MX h, MX norms) for a B-row decode step: the 17..32-row fp8 GEMV path with the packed fp8 weights.
+        MX h: the gate/up epilogue writes h as e4m3 with one E8M0 scale per 32 columns (mx_out) and the down GEMV reads
+        those block scales into its MFMAs (mx_in) -- no quantiser launch and no cross-workgroup row maximum.  MX norms:
+        the RMSNorms in front of the q|k|v, gate/up and lm_head GEMVs write MX rows of x*(1+w) with per-1024-column sums
+        of squares (pg_norm_residual_mx) and the GEMV applies rstd to its outputs -- no norm + row quantiser pair."""
         w = self.w
         L0 = w.tl[0]
-        mx_h = (self.FP8_GEMV and self._fp8_rows(B) and B <= 32 and self.MX_H and "gu_w8f" in L0
-                and "down_w8f" in L0 and w.inter % 128 == 0 and w.hidden <= 4096)
-        mx_n = (mx_h and self.MX_NORM and "qkv_w8f" in L0 and w.hidden % 1024 == 0
-                and getattr(w, "lm_w8f", None) is not None)
+        mx_h = (self._fp8_rows(B) and B <= 32 and "gu_w8f" in L0 and "down_w8f" in L0 and w.inter % 128 == 0
+                and w.hidden <= 4096)
+        mx_n = mx_h and "qkv_w8f" in L0 and w.hidden % 1024 == 0 and getattr(w, "lm_w8f", None) is not None
         return mx_h, mx_n
 
     def _ksplit(self, M: int, N: int, K: int) -> int:
         """split-K of an fp32-partial GEMM (fp8 operands: the kernels count K in byte pairs).  A GEMM that will
-        run as row blocks (_lin / _row_head) takes the split that suits its whole-tile head: the pt-448 x16
+        run as row blocks (_lin16 / _row_head) takes the split that suits its whole-tile head: the pt-448 x16
         down projection then runs 512 full-K tiles in 2 rounds instead of 1536 third-K tiles in 6, and two
         fewer fp32 slabs are written and re-read by the next RMSNorm."""
         if self._fp8_rows(M):
@@ -482,38 +446,46 @@ class PaliGemmaEngine:
         if m1:
             return m1
         Mh = M // 256 * 256
-        if self.ROW_BLOCKS and self.HEAD_KSPLIT and 0 < Mh < M:
+        if 0 < Mh < M:
             s = ops.gemm_ksplit(Mh, N, K)
             if self._row_head(M, N, s):
                 return s
         return ops.gemm_ksplit(M, N, K)
 
     def _tile_m1(self, M: int, name: str) -> int:
-        """split-K of a batch-1 prefill linear run as one row tile (PG_TILE_M1), 0 when it does not apply."""
-        if (not self.TILE_M1 or self.fp8 or self.tp != 1 or not 256 <= M <= 288
-                or M < self.PREFILL_ROWMAJOR_MIN_M):
+        """split-K of a batch-1 prefill linear run as one row tile (ops.TILE_M1), 0 when it does not apply."""
+        if self.fp8 or self.tp != 1 or not 256 <= M <= 288 or M < self.PREFILL_ROWMAJOR_MIN_M:
             return 0
         ks = self.TILE_M1_SPLIT.get(name, 0)
         K = self.w.inter if name == "down" else self.w.hidden
         return ks if ks * 64 <= K else 0
 
-    def _lin(self, x: torch.Tensor, Lw: dict, name: str, out: torch.Tensor, epi: int, M: int, ksplit: int = 1,
-             fa=None):
-        """One Gemma linear: bf16 (fragment-packed W) or, with fp8 weights and M > 16, the activation rows
-        quantised to e4m3 (pg_quant_fp8) feeding the PG_FP8 GEMM with the per-channel weight scales."""
-        if isinstance(x, tuple) and x[0] == "mx":  # MX rows (e4m3 + [M][K/32] block scales): the tile GEMM
+    def _lin(self, x, Lw: dict, name: str, out: torch.Tensor, epi: int, M: int, ksplit: int = 1, fa=None):
+        """One Gemma linear on M rows: fp8 (_lin8) when x comes as fp8 rows or the weights are fp8 and M > 16, else
+        bf16 (_lin16)."""
+        lin = self._lin8 if isinstance(x, tuple) or self._fp8_rows(M) else self._lin16
+        return lin(x, Lw, name, out, epi, M, ksplit, fa)
+
+    def _lin8(self, x, Lw: dict, name: str, out: torch.Tensor, epi: int, M: int, ksplit: int, fa):
+        """An fp8 Gemma linear (PG_FP8, per-channel weight scales).  x: ("mx", e4m3 rows, [M][K/32] block scales) for
+        the tile GEMM on MX rows; (e4m3 rows, row scales) from _norm or the attention kernel; or bf16 rows, quantised
+        here (pg_quant_fp8).  Up to 32 rows stream the fragment-packed weights (the fp8 GEMV) where the pack has them."""
+        if isinstance(x, tuple) and x[0] == "mx":
             return ops.gemm8(x[1], None, Lw[name + "_w8"], Lw[name + "_s8"], out, epi=epi, M=M, ksplit=ksplit, fa=fa,
                              mx_in=x[2])
-        if not isinstance(x, tuple) and self._fp8_rows(M):
+        if not isinstance(x, tuple):
             x8, xs = self._x8(M, x.shape[1])
             ops.quant_fp8(x, x8, xs, M=M)
-            x = (x8, xs)
-        if isinstance(x, tuple):        # fp8 rows (quantised here, by _norm, or by the attention kernel)
+        else:
             x8, xs = x
-            if self.FP8_GEMV and M <= 32 and name + "_w8f" in Lw:
-                return ops.gemm8(x8, xs, Lw[name + "_w8f"], Lw[name + "_s8"], out, epi=epi, M=M, ksplit=ksplit,
-                                 fa=fa, frag=True)
-            return ops.gemm8(x8, xs, Lw[name + "_w8"], Lw[name + "_s8"], out, epi=epi, M=M, ksplit=ksplit, fa=fa)
+        if M <= 32 and name + "_w8f" in Lw:
+            return ops.gemm8(x8, xs, Lw[name + "_w8f"], Lw[name + "_s8"], out, epi=epi, M=M, ksplit=ksplit, fa=fa,
+                             frag=True)
+        return ops.gemm8(x8, xs, Lw[name + "_w8"], Lw[name + "_s8"], out, epi=epi, M=M, ksplit=ksplit, fa=fa)
+
+    def _lin16(self, x: torch.Tensor, Lw: dict, name: str, out: torch.Tensor, epi: int, M: int, ksplit: int, fa):
+        """A bf16 Gemma linear: fragment-packed W, or from PREFILL_ROWMAJOR_MIN_M rows on the row-major copy -- as one
+        row tile (_tile_m1), as row blocks (_row_head: fp32 slabs, and gate/up), or as one launch."""
         W, flag = Lw[name + "_w"], self.w.wflag
         if M >= self.PREFILL_ROWMAJOR_MIN_M and name + "_wr" in Lw:
             W, flag = Lw[name + "_wr"], 0
@@ -521,11 +493,11 @@ class PaliGemmaEngine:
                 return ops.gemm(x, W, out, epi=epi | ops.TILE_M1, ksplit=ksplit)
         if fa is not None:
             return ops.gemm_fused(x, W, out, fa, epi=epi | flag, M=M)
-        if epi == ops.EPI_F32 and self.ROW_BLOCKS:
+        if epi == ops.EPI_F32:
             Mh = self._row_head(M, W.shape[0], ksplit)
             if Mh:
                 return self._lin_row_blocks(x, W, out, epi | flag, M, Mh, ksplit)
-        if epi == ops.EPI_BF16_GELU_MUL and self.ROW_BLOCKS and self.ROW_BLOCKS_GU:
+        if epi == ops.EPI_BF16_GELU_MUL:
             Mh = self._row_head(M, W.shape[0], 1)
             if Mh:      # gate/up at pt-448 x16: 8192 whole tiles (32 rounds) + a 128-row tail, not 33 rounds
                 ops.gemm(x[:Mh], W, out[:Mh], epi=epi | flag)
@@ -541,7 +513,7 @@ class PaliGemmaEngine:
         ops.gemm_fused(x[:Mh], W, out, fr, epi=epi, M=Mh, ksplit=ksplit, ldc=out.stride(-2))
         N, K, Mt = W.shape[0], W.shape[1], M - Mh
         st = max(ksplit, ops.split_for(math.ceil(Mt / 64) * math.ceil(N / 128), K // 64, max_split=8))
-        if st > ksplit and self.TAIL_SPLIT:
+        if st > ksplit:
             # the tail's own deeper split (its 64x128 tiles alone leave most CUs idle), summed into
             # slab 0's tail rows; the other slabs' tail rows are zeroed (the head never writes them)
             tp = self._buf("row_tail", (st, Mt, N), torch.float32)
@@ -599,10 +571,8 @@ class PaliGemmaEngine:
         if self.tp == 1:
             # (not where the bf16 GEMM runs as row blocks: its ragged tail takes a deeper split of its own, which a
             # one-split epilogue cannot -- pt-448 x16 prefill 82.9 -> 86.6 ms with it)
-            row_blocks = (not self._fp8_rows(T) and self.ROW_BLOCKS and
-                          self._row_head(T, self.w.hidden, 1) > 0)
-            if (resid is not None and self.PREFILL_RES and ks == 1 and T >= max(17, self.PREFILL_RES_MIN_M)
-                    and not row_blocks):
+            row_blocks = not self._fp8_rows(T) and self._row_head(T, self.w.hidden, 1) > 0
+            if resid is not None and ks == 1 and T >= max(17, self.PREFILL_RES_MIN_M) and not row_blocks:
                 self._lin(x, Lw, name, resid, ops.EPI_F32_RES, T)     # the residual add in the epilogue
                 return 0
             self._lin(x, Lw, name, part, ops.EPI_F32, T, ksplit=ks)
@@ -651,7 +621,7 @@ class PaliGemmaEngine:
             _, x8, xs, ss = xf
             return ops.gemm8(x8, None, w.lm_w8f, w.lm_s8, out, epi=ops.EPI_F32, M=rows, bias=w.lm_bias, frag=True,
                              mx_in=xs, ss_in=ss)
-        if self.FP8_GEMV and self._fp8_rows(rows) and rows <= 32 and getattr(w, "lm_w8f", None) is not None:
+        if self._fp8_rows(rows) and rows <= 32 and getattr(w, "lm_w8f", None) is not None:
             x8, xs = self._x8(rows, xf.shape[1])
             ops.quant_fp8(xf, x8, xs, M=rows)
             return ops.gemm8(x8, xs, w.lm_w8f, w.lm_s8, out, epi=ops.EPI_F32, M=rows, bias=w.lm_bias, frag=True)
@@ -684,8 +654,8 @@ class PaliGemmaEngine:
         return st
 
     def _decode_route(self, B: int) -> str:
-        """The form the layers of a B-row decode step take: "fin" (_decode_layers_fin), "fused"
-        (_decode_layers_fused) or "unfused" (_decode_layers_unfused)."""
+        """The route the layers of a B-row decode step take: "fin" (_decode_layers_fx at B <= FUSE_MAX_B,
+        _decode_layers_fin above), "fused" (_decode_layers_fused) or "unfused" (_decode_layers_unfused)."""
         fin_rows = B <= self.FUSE_MAX_B or self.FIN_MIN_B <= B <= 16
         if self.tp == 1 and self.USE_FIN and fin_rows and not self._fp8_rows(B):
             return "fin"
@@ -745,11 +715,12 @@ class PaliGemmaEngine:
             ops.embed_merge(st["ids"], None, w.embed, feats, feats.shape[0] if feats is not None else 0, ws.res_a,
                             **self._embed_kw())
         if ws.route == "fin":
-            xq, ss, tiles, n_ss = self._decode_layers_fin(st, cache, ws)
+            layers = self._decode_layers_fx if B <= self.FUSE_MAX_B else self._decode_layers_fin
+            xq, ss, tiles, n_ss = layers(st, cache, ws)
             # final RMSNorm folded into the lm_head GEMV: x' = resid*(1+w) from the last down_proj, rstd on the outputs
             logits = self._buf("d_logits", (B, w.vocab_local_pad), torch.float32)
             fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=ss, ss_ld=tiles, ss_n=n_ss, eps=1e-6)
-            lm_w, wf, nk = self._dec_w({"lm_w": w.lm_w, "lm_w13": w.lm_w13}, "lm", B, fx=self.DECODE_ADD == "fx")
+            lm_w, wf, nk = self._dec_w({"lm_w": w.lm_w, "lm_w13": w.lm_w13}, "lm", B)
             ops.gemm_fused(xq, lm_w, logits, fa, epi=ops.EPI_F32 | wf, M=B, bias=w.lm_bias, **nk)
             logits = logits[:, :w.vocab]
         else:
@@ -830,10 +801,10 @@ class PaliGemmaEngine:
                     akeys=ws.SK, **self._slot_kw(st, ws))
 
     def _decode_attn_merged(self, i: int, st: dict, cache: KVStore, ws, want_fp8: bool = False):
-        """Split-KV decode attention of layer i for B > FUSE_MAX_B rows, merged: one pg_attn_decode launch
-        (DECODE_FUSED_ATTN), else the split kernel + pg_attn_combine.  Returns the o_proj's input: the rows as bf16
-        [B][nh*hd], or with want_fp8, when the one-launch kernel can write them, as (e4m3, row scales) -- no
-        quantiser launch."""
+        """Split-KV decode attention of layer i for B > FUSE_MAX_B rows, merged: one pg_attn_decode launch, or where
+        that kernel does not apply (head_dim, a cache under 64 keys, fewer than FUSED_MIN_ROUNDS rounds per split) the
+        split kernel + pg_attn_combine.  Returns the o_proj's input: the rows as bf16 [B][nh*hd], or with want_fp8,
+        when the one-launch kernel can write them, as (e4m3, row scales) -- no quantiser launch."""
         w = self.w
         B = ws.B
         nh, nkv, hd = w.heads, w.kv_heads, w.head_dim
@@ -844,9 +815,9 @@ class PaliGemmaEngine:
         # per round trip, the four waves storing the split's partial) two rounds win too: pt-448 x16 1.348-1.351 vs
         # 1.391-1.392 ms/step (profiles/r05_fused_attn_pt448_ab.jsonl; round 4 measured 1.429 vs 1.412)
         plan = ops.decode_plan(B, nkv, cache.Smax)
-        if self.DECODE_FUSED_ATTN and hd in (32, 256) and cache.Smax >= 64 and plan[2] >= self.FUSED_MIN_ROUNDS:
+        if hd in (32, 256) and cache.Smax >= 64 and plan[2] >= self.FUSED_MIN_ROUNDS:
             x8 = None
-            if want_fp8 and self.ATTN_FP8_OUT and ops.attn_decode_q8_ok(nh, nkv, hd, plan[1]):
+            if want_fp8 and ops.attn_decode_q8_ok(nh, nkv, hd, plan[1]):
                 x8 = self._x8(B, nh * hd)
             ops.attn_decode(ws.qb, nh * hd, attn, nh * hd, cache.kd[i], cache.vd[i],
                             B=B, Lkv=0 if ws.ragged else 1, lkv_dev=st["pos"] if ws.ragged else st["kv_len"],
@@ -904,110 +875,98 @@ class PaliGemmaEngine:
             ns = self._allreduce_slabs(part, ws.sd)
         return ns
 
-    def _dec_w(self, d, name: str, B: int, ksplit: int = 1, fx: bool = True):
-        """(W, layout flag, N / K keywords) of the decode launch of d[name + "_w"] at B rows on the fin route: the 13-bit
-        pack when the switch is on, the matrix has one, the launch is a batch-1 form of the fixed-point route (fx) and
-        every wave of a split owns whole 128-k blocks; else the bf16 fragment pack, as before."""
+    def _dec_w(self, d, name: str, B: int, ksplit: int = 1):
+        """(W, layout flag, N / K keywords) of the decode launch of d[name + "_w"] at B rows on the fx / fin routes: the
+        13-bit pack (its 12-bit form for a launch in w12_forms) when the switch is on, the matrix has one, the launch is
+        a B <= FUSE_MAX_B form and every wave of a split owns whole 128-k blocks; else the bf16 fragment pack."""
         W = d[name + "_w"]
         p13 = d.get(name + "_w13")
-        if (self.W13 and fx and p13 is not None and name in self.W13_FORMS and B <= self.FUSE_MAX_B and self.tp == 1
+        if (self.W13 and p13 is not None and name in self.W13_FORMS and B <= self.FUSE_MAX_B and self.tp == 1
                 and (W.shape[1] // 64) % (8 * ksplit) == 0):
             f12 = ops.W_FRAG12 if name in getattr(self.w, "w12_forms", ()) else 0
             return p13, ops.W_FRAG13 | f12, dict(N=W.shape[0], K=W.shape[1])
         return W, self.w.wflag, {}
 
-    def _decode_layers_fin(self, st: dict, cache: KVStore, ws):
-        """Decode layers (single rank, B <= FUSE_MAX_B) in 5 launches with in-kernel split-K finalisation:
-        o_proj and down_proj add their split-K slabs into the residual in place (the last-arriving split of
-        each 16-column tile), and write x' = bf16(resid*(1+w_next)) plus per-tile sums of squares; the next
-        GEMV (gate/up, the next layer's qkv, finally the lm_head) reads x' like a plain activation and
-        scales its outputs by rstd (RMSNorm: W.(x*rstd*(1+w)) = rstd * W.(x*(1+w))).
-        At B > FUSE_MAX_B (up to 16 rows) the split-KV merge runs as its own kernel (folded into every o_proj
-        workgroup it would be recomputed per workgroup) and the GEMVs run two 16-row tiles per workgroup, so
-        the sums of squares come one per tile pair.
+    def _decode_layers_fx(self, st: dict, cache: KVStore, ws):
+        """Decode layers (single rank, bf16, B <= FUSE_MAX_B), 5 launches each, on a fixed-point residual: o_proj and
+        down_proj add their split-K partials into an int64 accumulator with integer atomics (EPI_FX_ADD: the sum is
+        exact, so decode is bit-reproducible run to run), and every GEMV that follows normalises the accumulator in its
+        prologue (PRO_RMSNORM, fx=).  Layer 0's q|k|v GEMV reads the embedding rows instead and clears the accumulator;
+        layer 0's o_proj folds those rows in, so from there on the accumulator holds the whole residual.  o_proj also
+        merges the split-KV partials in its prologue.  The last layer's down_proj finalises in-kernel (EPI_F32_FIN with
+        fx=: adds the accumulator, clears it, writes x' = bf16(resid*(1+w_final)) and per-tile sums of squares) for
+        the lm_head.  gate/up, down and the lm_head stream the 13- / 12-bit weight packs (_dec_w).
         Returns (x', sums of squares, their row stride, entries per row) of the final norm for the lm_head."""
         w = self.w
-        B, res, part = ws.B, ws.res_a, ws.part
-        H = w.hidden
-        tiles = (H + 15) // 16
-        merge_in_gemv = B <= self.FUSE_MAX_B
-        # "fx": the partials go to the fixed-point accumulator (zero between steps: the last layer's F32_FIN clears it);
-        # layer 0's o_proj also folds the embedding rows in, so from there on it holds the whole residual
-        fx = self._zeros("d_fx", (B, H), torch.int64) if merge_in_gemv and self.DECODE_ADD == "fx" else None
-        f = SimpleNamespace(                        # what _mlp_fin shares with this loop
-            tiles=tiles,
-            n_ss=tiles if B <= 4 else (tiles + 1) // 2,         # one entry per GEMV workgroup (M > 4: tile pairs)
-            cnt=self._zeros("d_fin_cnt", (tiles,), torch.int32),
-            ss_o=self._buf("d_ss_o", (B, tiles), torch.float32),
-            ss_d=self._buf("d_ss_d", (B, tiles), torch.float32),
-            xq=self._buf("d_xq", (B, H), torch.bfloat16),
-            add_down=merge_in_gemv and self.DECODE_ADD in ("down", "both", "fx"),
-            add_o=merge_in_gemv and self.DECODE_ADD in ("both", "fx"),
-            fx=fx,
-            fx_st=self.fx_status() if fx is not None else None,  # set by an FX_ADD launch given an unholdable value
-            add_epi=ops.EPI_FX_ADD if fx is not None else ops.EPI_F32_ADD,
-            add_dst=fx if fx is not None else res)
-        fin_o = dict(fin_cnt=f.cnt, fin_resid=res, ss_out=f.ss_o, ss_ld=tiles, fin_x=f.xq)  # o_proj's F32_FIN fields
+        B, res = ws.B, ws.res_a
+        tiles = (w.hidden + 15) // 16
+        fx = self._zeros("d_fx", (B, w.hidden), torch.int64)    # zero between steps: the finalising down clears it
+        status = self.fx_status()                               # set by an FX_ADD launch given an unholdable value
+        xq = self._buf("d_xq", (B, w.hidden), torch.bfloat16)
+        ss = self._buf("d_ss_d", (B, tiles), torch.float32)
+        for i, Lw in enumerate(w.tl):
+            fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, nsplit=0, norm_w=Lw["in_w"], eps=1e-6,
+                                **self._rope_kw(i, st, cache, ws))
+            if i == 0:
+                # the step starts from a zero accumulator whatever an earlier (interrupted) step left in it: layer 0's
+                # q|k|v GEMV does not read it and clears it before layer 0's o_proj adds into it (ADVICE r5)
+                fa.resid_in, fa.amax_zero, fa.amax_zero_n = res.data_ptr(), fx.data_ptr(), fx.numel() * 2
+            else:
+                fa.fx = fx.data_ptr()
+            qkv_w, wf, nk = self._dec_w(Lw, "qkv", B)
+            ops.gemm_fused(None, qkv_w, ws.qb, fa, epi=ops.EPI_QKV_ROPE | wf | ws.sr, M=B, **nk)
+            self._attn_split(i, st, cache, ws)
+            fa = ops.fused_args(resid_in=res if i == 0 else None, status=status, **self._combine_kw(st, ws))
+            o_w, wf, nk = self._dec_w(Lw, "o", B, ws.so)
+            ops.gemm_fused(None, o_w, fx, fa, epi=ops.EPI_FX_ADD | wf | ws.sr, M=B, ksplit=ws.so, **nk)
+            fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, fx=fx, nsplit=0, norm_w=Lw["post_w"], eps=1e-6)
+            gu_w, wf, nk = self._dec_w(Lw, "gu", B)
+            ops.gemm_fused(None, gu_w, ws.h, fa, epi=ops.EPI_BF16_GELU_MUL | wf, M=B, **nk)
+            down_w, wf, nk = self._dec_w(Lw, "down", B, ws.sd)
+            if i + 1 < len(w.tl):
+                ops.gemm_fused(ws.h, down_w, fx, ops.fused_args(status=status), epi=ops.EPI_FX_ADD | wf, M=B,
+                               ksplit=ws.sd, **nk)
+            else:
+                fa = ops.fused_args(fin_cnt=self._zeros("d_fin_cnt", (tiles,), torch.int32), fin_resid=res, ss_out=ss,
+                                    ss_ld=tiles, fin_x=xq, norm_w=w.final_w, fx=fx)
+                ops.gemm_fused(ws.h, down_w, ws.part, fa, epi=ops.EPI_F32_FIN | wf, M=B, ksplit=ws.sd, **nk)
+        return xq, ss, tiles, tiles if B <= 4 else (tiles + 1) // 2
+
+    def _decode_layers_fin(self, st: dict, cache: KVStore, ws):
+        """Decode layers (single rank, bf16, more than FUSE_MAX_B and up to 16 rows), 5 launches each, with in-kernel
+        split-K finalisation: o_proj and down_proj add their split-K slabs into the residual in place (the
+        last-arriving split of each 16-column tile, EPI_F32_FIN), and write x' = bf16(resid*(1+w_next)) plus per-tile
+        sums of squares; the next GEMV (gate/up, the next layer's q|k|v, finally the lm_head) reads x' like a plain
+        activation and scales its outputs by rstd (PRO_X_RSTD; RMSNorm: W.(x*rstd*(1+w)) = rstd * W.(x*(1+w))).  Only
+        layer 0's q|k|v GEMV normalises itself (PRO_RMSNORM, the embedding rows).  The split-KV merge runs as its own
+        kernel (_decode_attn_merged: folded into every o_proj workgroup it would be recomputed per workgroup), and
+        above 4 rows the GEMVs run two 16-column tiles per workgroup, so the sums of squares come one per tile pair.
+        Returns (x', sums of squares, their row stride, entries per row) of the final norm for the lm_head."""
+        w = self.w
+        B, res, part, wflag = ws.B, ws.res_a, ws.part, w.wflag
+        tiles = (w.hidden + 15) // 16
+        n_ss = tiles if B <= 4 else (tiles + 1) // 2            # one entry per GEMV workgroup
+        cnt = self._zeros("d_fin_cnt", (tiles,), torch.int32)
+        ss_o = self._buf("d_ss_o", (B, tiles), torch.float32)
+        ss_d = self._buf("d_ss_d", (B, tiles), torch.float32)
+        xq = self._buf("d_xq", (B, w.hidden), torch.bfloat16)
         for i, Lw in enumerate(w.tl):
             rope = self._rope_kw(i, st, cache, ws)
-            if i == 0 or f.add_down:  # the residual rows are final (embedding, or atomically added): RMSNorm prologue
-                # (fx mode: layer 0 reads the embedding rows; from layer 0's o_proj on the accumulator holds the whole
-                # residual -- that launch folds res in -- and the consumers read it alone)
-                fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res if (i == 0 or fx is None) else None,
-                                    fx=fx if i > 0 else None, nsplit=0, norm_w=Lw["in_w"], eps=1e-6, **rope)
-                if i == 0 and fx is not None:
-                    # the step starts from a zero accumulator whatever an earlier (interrupted) step left in it: layer 0's
-                    # q|k|v GEMV does not read it and clears it before layer 0's o_proj adds into it (ADVICE r5)
-                    fa.amax_zero, fa.amax_zero_n = fx.data_ptr(), fx.numel() * 2
-                qkv_w, wf, nk = self._dec_w(Lw, "qkv", B, fx=fx is not None)
-                ops.gemm_fused(None, qkv_w, ws.qb, fa, epi=ops.EPI_QKV_ROPE | wf | ws.sr, M=B, **nk)
+            if i == 0:
+                fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res, nsplit=0, norm_w=Lw["in_w"], eps=1e-6, **rope)
+                ops.gemm_fused(None, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | wflag | ws.sr, M=B)
             else:
-                fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=f.ss_d, ss_ld=tiles, ss_n=f.n_ss, eps=1e-6, **rope)
-                ops.gemm_fused(f.xq, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | w.wflag | ws.sr, M=B)
-            if not merge_in_gemv:
-                attn = self._decode_attn_merged(i, st, cache, ws)
-                fa = ops.fused_args(norm_w=Lw["post_w"], **fin_o)
-                ops.gemm_fused(attn, Lw["o_w"], part, fa, epi=ops.EPI_F32_FIN | w.wflag, M=B, ksplit=ws.so)
-            else:
-                self._attn_split(i, st, cache, ws)
-                if f.add_o:
-                    fa = ops.fused_args(resid_in=res if (fx is not None and i == 0) else None, status=f.fx_st,
-                                        **self._combine_kw(st, ws))
-                    o_w, wf, nk = self._dec_w(Lw, "o", B, ws.so, fx=fx is not None)
-                    ops.gemm_fused(None, o_w, f.add_dst, fa, epi=f.add_epi | wf | ws.sr, M=B, ksplit=ws.so, **nk)
-                else:
-                    fa = ops.fused_args(norm_w=Lw["post_w"], **fin_o, **self._combine_kw(st, ws))
-                    ops.gemm_fused(None, Lw["o_w"], part, fa, epi=ops.EPI_F32_FIN | w.wflag | ws.sr, M=B,
-                                   ksplit=ws.so)
-            self._mlp_fin(i, ws, f)
-        return f.xq, f.ss_d, tiles, f.n_ss
-
-    def _mlp_fin(self, i: int, ws, f):
-        """gate/up + down of layer i of _decode_layers_fin (f: its buffers and flags): x' = f.xq with rstd from f.ss_o
-        -> h -> down, finalised into the residual (x' of the next norm -> f.xq, its sums of squares -> f.ss_d).
-        f.add_down (every layer but the last): down adds its partials into the residual with float atomics
-        (EPI_F32_ADD), or into the fixed-point accumulator f.fx (EPI_FX_ADD); the next GEMV normalises the residual
-        (+ fx) itself.  f.add_o: o_proj did so, gate/up normalises the residual (+ fx).  The finalising form adds fx
-        and clears it."""
-        w = self.w
-        Lw, last = w.tl[i], i + 1 == len(w.tl)
-        B, res, fx = ws.B, ws.res_a, f.fx
-        if f.add_o:
-            fa = ops.fused_args(pro_mode=ops.PRO_RMSNORM, resid_in=res if fx is None else None, fx=fx, nsplit=0,
-                                norm_w=Lw["post_w"], eps=1e-6)
-            gu_w, wf, nk = self._dec_w(Lw, "gu", B, fx=fx is not None)
-            ops.gemm_fused(None, gu_w, ws.h, fa, epi=ops.EPI_BF16_GELU_MUL | wf, M=B, **nk)
-        else:
-            fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=f.ss_o, ss_ld=f.tiles, ss_n=f.n_ss, eps=1e-6)
-            ops.gemm_fused(f.xq, Lw["gu_w"], ws.h, fa, epi=ops.EPI_BF16_GELU_MUL | w.wflag, M=B)
-        down_w, wf, nk = self._dec_w(Lw, "down", B, ws.sd, fx=fx is not None)
-        if f.add_down and not last:
-            ops.gemm_fused(ws.h, down_w, f.add_dst, ops.fused_args(status=f.fx_st), epi=f.add_epi | wf, M=B,
-                           ksplit=ws.sd, **nk)
-            return
-        nxt_w = w.final_w if last else w.tl[i + 1]["in_w"]
-        fa = ops.fused_args(fin_cnt=f.cnt, fin_resid=res, ss_out=f.ss_d, ss_ld=f.tiles, fin_x=f.xq, norm_w=nxt_w, fx=fx)
-        ops.gemm_fused(ws.h, down_w, ws.part, fa, epi=ops.EPI_F32_FIN | wf, M=B, ksplit=ws.sd, **nk)
+                fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=ss_d, ss_ld=tiles, ss_n=n_ss, eps=1e-6, **rope)
+                ops.gemm_fused(xq, Lw["qkv_w"], ws.qb, fa, epi=ops.EPI_QKV_ROPE | wflag | ws.sr, M=B)
+            attn = self._decode_attn_merged(i, st, cache, ws)
+            fa = ops.fused_args(fin_cnt=cnt, fin_resid=res, ss_out=ss_o, ss_ld=tiles, fin_x=xq, norm_w=Lw["post_w"])
+            ops.gemm_fused(attn, Lw["o_w"], part, fa, epi=ops.EPI_F32_FIN | wflag, M=B, ksplit=ws.so)
+            fa = ops.fused_args(pro_mode=ops.PRO_X_RSTD, ss_in=ss_o, ss_ld=tiles, ss_n=n_ss, eps=1e-6)
+            ops.gemm_fused(xq, Lw["gu_w"], ws.h, fa, epi=ops.EPI_BF16_GELU_MUL | wflag, M=B)
+            nxt_w = w.tl[i + 1]["in_w"] if i + 1 < len(w.tl) else w.final_w
+            fa = ops.fused_args(fin_cnt=cnt, fin_resid=res, ss_out=ss_d, ss_ld=tiles, fin_x=xq, norm_w=nxt_w)
+            ops.gemm_fused(ws.h, Lw["down_w"], part, fa, epi=ops.EPI_F32_FIN | wflag, M=B, ksplit=ws.sd)
+        return xq, ss_d, tiles, n_ss
 
     def _split_keys(self, B: int, Smax: int) -> int:
         """Keys per decode-attention split: 32 (one MFMA block) at small batch; at B > FUSE_MAX_B (separate

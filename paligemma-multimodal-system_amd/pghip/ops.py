@@ -353,15 +353,12 @@ def decode_cache_pack(k: torch.Tensor, vt: torch.Tensor, Hkv: int):
     return kd, vd
 
 
-PF_KEYSPLIT = os.environ.get("PG_PF_KEYSPLIT", "1") != "0"
-
-
 def prefill_key_splits(B: int, Lq: int, Lkv: int, Hq: int, Hkv: int) -> int:
     """Key splits for an unmasked prefill attention whose grid of 64-row workgroups leaves most CUs idle (batch 1:
     pt-224 Gemma 33 workgroups, SigLIP 64): as many splits (<= 8, >= one 64-key block each) as keep the split grid
     within one round; 1 = unsplit.  Each split writes (O, m, l) partials that pg_attention merges itself."""
     wgs = math.ceil(Lq * (Hq // Hkv) / 64) * Hkv * B
-    if not PF_KEYSPLIT or wgs >= 128:
+    if wgs >= 128:
         return 1
     return max(1, min(8, 256 // wgs, math.ceil(Lkv / 64)))
 
@@ -395,7 +392,7 @@ def attn_probs(q, q_rs, k, k_bs, k_hs, k_rs, *, B, Lq, Lkv, Hq, Hkv, D, scale, m
     return out
 
 
-DECODE_MAX_SPLITS = int(os.environ.get("PG_DECODE_MAX_SPLITS", "8"))
+DECODE_MAX_SPLITS = 8       # splits per (row, kv head) of pg_attn_decode: its last split merges every partial alone
 
 
 def decode_plan(B: int, Hkv: int, kcap: int):

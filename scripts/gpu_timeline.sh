@@ -1,5 +1,5 @@
 # decode step kernel timeline (rocprofv3 kernel trace) for each "name|ENV=VAL ...|decode_step.py args" case in CASES
-#   gpurun -- 'CASES="mx1|PG_MX_NORM=1|--config pt-896 --batch 32 --fp8;mx0|PG_MX_NORM=0|--config pt-896 --batch 32 --fp8" bash scripts/gpu_timeline.sh <out>'
+#   CASES="w13|PG_W13=1|--config pt-224;frag|PG_W13=0|--config pt-224" bash scripts/gpu_timeline.sh <out>
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp

@@ -44,7 +44,7 @@ ids, px = ids.cuda(), px.cuda()
 T = a.steps + 1
 cache, feats, logits, nxt = eng.prefill_request(ids, px, torch.ones_like(ids), T + 8)
 sampler = dict(do_sample=False)
-st = eng.decode_state(B, cache, nxt, T + 8, sampler=sampler)      # chained unless PG_CHAIN_EMBED=0
+st = eng.decode_state(B, cache, nxt, T + 8, sampler=sampler)      # chained (engine.CHAIN_EMBED)
 eng.sample(logits, st, sampler, advance=False, feats=feats)
 replay = eng._graph_step(st, cache, feats, sampler)
 snap = {k: st[k].clone() for k in ("ids", "pos", "kv_len", "step")}

@@ -1,7 +1,8 @@
 """Batch-1 prefill (vision + merge + Gemma + first token) of the bench workload: GPU time per prefill (HIP
-events over R back-to-back prefills) and the host time to issue them, alternating engine knobs in-process.
+events over R back-to-back prefills) and the host time to issue them; with --knob, alternating a boolean engine
+attribute (CHAIN_EMBED, USE_FIN, W13) on and off in-process.
 
-    python scripts/tune/prefill_time.py [--config pt-224] [--reps 20] [--knob TILE_M1]
+    python scripts/tune/prefill_time.py [--config pt-224] [--reps 20] [--knob NAME]
 
 A host issue time close to the GPU time means the eager prefill is launch-bound, not kernel-bound."""
 import argparse
@@ -17,7 +18,7 @@ import torch  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="pt-224")
 ap.add_argument("--reps", type=int, default=20)
-ap.add_argument("--knob", default="TILE_M1", help="boolean engine class attribute toggled on / off")
+ap.add_argument("--knob", default=None, help="boolean engine class attribute toggled on / off (default: none)")
 a = ap.parse_args()
 
 from pghip import configs, engine, synthetic, weights  # noqa: E402
@@ -31,8 +32,10 @@ ids, px = ids.cuda(), px.cuda()
 run = bench.Runner(eng, ids, px, 8, dict(do_sample=False))
 res = {"config": a.config, "knob": a.knob}
 for rnd in range(3):
-    for on in (True, False):
-        setattr(eng, a.knob, on)
+    for on in (True, False) if a.knob else (None,):
+        if a.knob:
+            setattr(eng, a.knob, on)
+        tag = f"{a.knob}={int(on)}" if a.knob else "prefill"
         run.prefill_run()
         torch.cuda.synchronize()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -44,10 +47,11 @@ for rnd in range(3):
         ev[1].record()
         torch.cuda.synchronize()
         gpu = ev[0].elapsed_time(ev[1]) / a.reps
-        res.setdefault(f"{a.knob}={int(on)}", []).append([round(gpu, 3), round(host, 3)])
-        print(f"{a.knob}={int(on)} prefill {gpu:.3f} ms (host issue {host:.3f} ms)", flush=True)
+        res.setdefault(tag, []).append([round(gpu, 3), round(host, 3)])
+        print(f"{tag} {gpu:.3f} ms (host issue {host:.3f} ms)", flush=True)
 # the same prefill replayed from one captured hipGraph (bench.py --graph-prefill): no host launches in the timing
-setattr(eng, a.knob, True)
+if a.knob:
+    setattr(eng, a.knob, True)
 g = torch.cuda.CUDAGraph()
 run.prefill_run()
 torch.cuda.synchronize()

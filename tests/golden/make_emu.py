@@ -1,11 +1,11 @@
 """Operand-rounding emulation fixtures from the numpy ORACLE (not the reference): the fp32 oracle run with the HIP
 fp8 path's operand rounding -- bf16 operands everywhere, e4m3 Gemma linears and tied lm_head with per-row /
 per-channel scales (oracle.paligemma_oracle.fp8_operands; min_rows=0: prefill and batch > 16 decode both run fp8;
-mx_h / mx_norm: the decode down_proj and the RMSNorm-fed decode linears on MX rows, engine.MX_H / MX_NORM) -- on a reference
-golden's requests, teacher-forced with the reference's own greedy ids.  Stored per image and step: the emulated
-logits at the reference's top-64 ids, the emulated argmax and top1-top2 margin.  tests/test_large_gpu.py bounds the
-HIP fp8 path's distance to the reference by 1.5x this intrinsic distance (the bf16 tests do the same with
-oracle.bf16_operands live).
+mx_h / mx_norm: the decode down_proj and the RMSNorm-fed decode linears on MX rows, as the engine's 17..32-row fp8
+decode) -- on a reference golden's requests, teacher-forced with the reference's own greedy ids.  Stored per image
+and step: the emulated logits at the reference's top-64 ids, the emulated argmax and top1-top2 margin.
+tests/test_large_gpu.py bounds the HIP fp8 path's distance to the reference by 1.5x this intrinsic distance (the bf16
+tests do the same with oracle.bf16_operands live).
 
 --tp W (round 6): the tensor-parallel form (oracle fp8_operands(tp=W): the row-parallel o_proj / down_proj quantised
 per rank on their K slices and summed in rank order) -> <golden>_fp8emu_tp<W>.npz, the bound of the TP=W GPU test

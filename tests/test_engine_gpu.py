@@ -214,13 +214,12 @@ def test_pt224_decode_bit_reproducible_run_to_run(golden):
     """The same full-size PaliGemma-3B-224 request decoded three times in one process -- eager steps, hipGraph
     replays, eager again -- gives bitwise-equal logits at every step and the same ids (greedy ids
     must not depend on the run).  Batch-1 decode adds the o_proj / down_proj split-K partials into the residual with
-    atomics whose arrival order varies; the default fixed-point accumulator (PG_EPI_FX_ADD, engine.DECODE_ADD "fx")
+    atomics whose arrival order varies; the default fixed-point accumulator (PG_EPI_FX_ADD, engine._decode_layers_fx)
     makes that sum exact, so nothing downstream can differ.  The prefill logits are compared too."""
     from pghip import configs, engine, synthetic, weights
     g = golden("pt224")
     cfg = configs.PT_224
     eng = engine.PaliGemmaEngine(cfg, weights.PackedWeights(cfg, synthetic.SyntheticStateDict(cfg).__getitem__))
-    assert eng.DECODE_ADD == "fx"
     ids = torch.from_numpy(g["input_ids"]).cuda()
     px = torch.from_numpy(g["pixel_values"]).cuda()
     steps, V = 24, eng.w.vocab
@@ -255,7 +254,6 @@ def test_decode_step_starts_from_a_clean_fx_accumulator(tiny, golden):
     a zero accumulator, because layer 0's q|k|v GEMV clears it (PgFusedArgs.amax_zero on the bf16 GEMV, ABI 12) before
     any FX_ADD producer adds into it.  And a status word set by an overflowing FX_ADD makes generate() raise."""
     eng, _ = tiny
-    assert eng.DECODE_ADD == "fx"
     g = golden("tiny")
     ids = torch.from_numpy(g["b1_input_ids"]).cuda()
     px = torch.from_numpy(g["b1_pixel_values"]).cuda()

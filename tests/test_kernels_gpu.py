@@ -1066,7 +1066,7 @@ def _mx_deq(q8, sc, M, K):
 @pytest.mark.parametrize("M,I,H,ks", [(32, 16384, 2048, 8), (32, 2048, 2048, 1), (17, 4096, 1024, 2),
                                       (24, 2048, 512, 1), (9, 256, 512, 1), (32, 16384, 2048, 16)])
 def test_mx_h_gate_up_and_down(M, I, H, ks):
-    """The batched fp8 decode MLP on MX rows (ABI 11, engine.MX_H): the gate/up GEMV writes h as e4m3 bytes with one
+    """The batched fp8 decode MLP on MX rows (ABI 11): the gate/up GEMV writes h as e4m3 bytes with one
     E8M0 scale per 32 columns (mx_out) -- bit-identical to the torch MX rule applied to the bf16 gelu*up launch's h --
     and the down GEMV reading those block scales into its MFMAs (mx_in; the wide and the K-split forms) equals a torch
     fp32 matmul of the dequantised operands up to summation order; also on scales spread over 2^-10 .. 2^10."""
@@ -1099,7 +1099,7 @@ def test_mx_h_gate_up_and_down(M, I, H, ks):
 @pytest.mark.parametrize("M,I,H,ks", [(300, 1024, 512, 1), (33, 2048, 2048, 2), (1100, 16384, 2048, 3),
                                       (4200, 4096, 1024, 1)])
 def test_mx_h_prefill_tiles(M, I, H, ks):
-    """The fp8 prefill MLP on MX rows (ABI 12, engine.MX_PREFILL): the 128 x 128 fp8 gate/up tile writes h as e4m3
+    """The fp8 prefill MLP on MX rows (ABI 12): the 128 x 128 fp8 gate/up tile writes h as e4m3
     with one E8M0 scale per 32 columns, natural layout [M][I/32] -- bit-identical to the torch MX rule on the bf16
     gelu*up tile's h (one e4m3 step allowed where the two launches' bf16 h differ by an ulp) -- and the 256 x 256 fp8
     fp32-slab GEMM reading those block scales beside the rows (mx_in) equals a float64 matmul of the dequantised
@@ -1137,7 +1137,7 @@ def test_mx_h_prefill_tiles(M, I, H, ks):
 @pytest.mark.parametrize("M,H,nsplit,I", [(32, 2048, 8, 16384), (17, 2048, 2, 4096), (24, 3072, 0, 1024),
                                           (32, 2048, 11, 2048), (20, 1024, 1, 2048)])
 def test_mx_norm_rows_and_rstd_consumers(M, H, nsplit, I):
-    """pg_norm_residual_mx (ABI 11, engine.MX_NORM): the residual update equals resid + the slabs in slab order
+    """pg_norm_residual_mx (ABI 11, 17..32 fp8 rows): the residual update equals resid + the slabs in slab order
     (bitwise), the e4m3 rows and E8M0 block scales equal the torch MX rule on x*(1+w) (bitwise), the per-256-column
     sums of squares (per 1024 columns) match; an fp8 GEMV fed those rows (mx_in + ss_in) equals rstd * the fp32 matmul of the dequantised
     rows -- the RMSNorm split at rstd -- for the fp32 slab and the gelu*up (with MX h out) epilogues."""
